@@ -1,9 +1,16 @@
 #!/usr/bin/env python3
 """Headline benchmark: device-resident GF(2^8) encode of 10+4 x 16 MiB stripes.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does only what the headline figure needs: it fills the inputs,
+warms up, times K steps and prints the result line.  --dump-outputs DIR also
+writes a fixed, seeded sample of the parity the last timed step left in HBM to
+DIR/parity_sample.npy (float32), so two builds can be compared byte for byte.
+--full adds everything else: the correctness gate against the reference
+digests, the CPU baselines and every extra leg listed below.
 
 Metric (BASELINE.json): "device-resident encode MB/s (data+parity)" -- bytes of
 data + parity shards per second, MB = 2^20 (the reference's unit,
@@ -15,9 +22,9 @@ bytes); stripes are split across ranks with no data-path collective
 ("scaling": "weak").  Inputs are resident in HBM before the timed region.
 
 Also reported (not `value`): the kernel's HBM roofline fraction (HIP events on
-the launch stream), the reference's own SIMD CPU path on this host (rank 0,
-N = 1, bounded sample), reconstruct of 2 erased data shards, and the
-pinned-host end-to-end rate (PCIe-inclusive).
+the launch stream of the timed steps) and, with --full, the reference's own
+SIMD CPU path on this host (rank 0, N = 1, bounded sample), reconstruct of 2
+erased data shards, and the pinned-host end-to-end rate (PCIe-inclusive).
 """
 from __future__ import annotations
 
@@ -41,6 +48,12 @@ METRIC = "device-resident encode MB/s (data+parity), 10+4 × 16 MiB shards, 1/2/
 MiB = 1 << 20
 HBM_PEAK_GBPS = 8000.0  # MI355X HBM3E spec (MI355X_MICROARCH.md chip table)
 SEED = 0x5EED
+FULL_OUT_DIR = "bench_out"  # under the repository root; kept out of git
+# --dump-outputs: one block of DUMP_BLOCK consecutive bytes of every parity
+# shard of every resident stripe, at an offset drawn from a generator seeded
+# with SEED (512 stripes x 4 shards x 4 KiB = 8 Mi values, 32 MB as float32)
+DUMP_BLOCK = 4096
+DUMP_LIMIT = 64 * 1000 * 1000  # bytes of .npy payload, at most
 
 
 def parse(argv=None):
@@ -52,12 +65,18 @@ def parse(argv=None):
     ap.add_argument("--parity-shards", type=int, default=4)
     ap.add_argument("--shard-mib", type=int, default=16)
     ap.add_argument("--stripes", type=int, default=512, help="stripes per GPU per step")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write a seeded sample of the last step's "
+                         "parity to DIR/parity_sample.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the correctness gate, the CPU baselines and every extra leg")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip reconstruct / e2e legs")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip reconstruct / e2e legs")
     ap.add_argument("--full-out", default=None,
-                    help="where the full results (every leg) go; default "
-                         "gpurun_out/bench_full_n<N>.json")
+                    help="where the full results (every leg) go; default with --full: "
+                         f"{FULL_OUT_DIR}/bench_full_n<N>.json, without it: not written")
     return ap.parse_args(argv)
 
 
@@ -462,17 +481,20 @@ def compact_line(line, full, full_path):
 
 def emit_results(line, cpu, extras, path):
     """Writes the full results (line + CPU legs + every extra leg) to `path`
-    and prints the compact line as the last stdout line."""
+    (None: a plain run, nothing to write) and prints the compact line as the
+    last stdout line."""
     full = dict(line)
     for key in ("cpu_baseline_legs", "cpu_host"):
         if key in cpu:
             full[key] = cpu[key]
     full.update(extras)
-    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    with open(path, "w") as f:
-        json.dump(full, f, indent=1)
-    shown = os.path.relpath(os.path.abspath(path), ROOT)
-    print(f"full results (every leg): {shown}", file=sys.stderr, flush=True)
+    shown = None
+    if path is not None:
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        with open(path, "w") as f:
+            json.dump(full, f, indent=1)
+        shown = os.path.relpath(os.path.abspath(path), ROOT)
+        print(f"full results (every leg): {shown}", file=sys.stderr, flush=True)
     out = compact_line(line, full, shown)
     print(json.dumps(out), flush=True)
     return out
@@ -498,6 +520,34 @@ def check_stripes(v, mine, resident, k, p):
         checked.append(g)
         ok = ok and got == gold[str(g)]
     return (1 if ok else 0) if checked else -1, checked
+
+
+def dump_outputs(v, k, p, out_dir, rank, world):
+    """--dump-outputs: what the timed path left for its caller, sampled.  The
+    path's output is the parity of the resident stripes in the stripe view
+    v[stripe, shard, byte] (32 GiB at the default size), so this writes one
+    block of DUMP_BLOCK consecutive bytes of every parity shard of every
+    stripe, each at an offset drawn from a generator seeded with SEED, as
+    float32 [stripe x shard, byte] to out_dir/parity_sample.npy (one file per
+    rank, named by rank, when N > 1).  Past DUMP_LIMIT bytes a seeded subset
+    of the shards is kept.  The same arguments give the same inputs, shards
+    and offsets in every run and build."""
+    import numpy as np
+    import torch
+    n, T, L = v.shape
+    block = min(DUMP_BLOCK, L)
+    pairs = n * p
+    keep = min(pairs, DUMP_LIMIT // (4 * block))
+    rng = np.random.default_rng(SEED)
+    which = np.sort(rng.choice(pairs, keep, replace=False)) if keep < pairs else np.arange(pairs)
+    offs = rng.integers(0, L - block + 1, size=keep)
+    base = ((which // p) * T + k + which % p) * L + offs  # into the flat buffer
+    idx = torch.from_numpy(base).to(v.device)[:, None] + torch.arange(block, device=v.device)
+    sample = v.reshape(-1)[idx].to(torch.float32).cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    name = "parity_sample.npy" if world == 1 else f"parity_sample_rank{rank}.npy"
+    np.save(os.path.join(out_dir, name), sample)
+    return os.path.join(out_dir, name)
 
 
 def gather(values, world, rank, device):
@@ -538,7 +588,9 @@ def host_leg(r, v, k, p, L, stream, world, rank, coll_dev):
 
 
 def main(argv=None):
+    global _jit_deadline
     args = parse(argv)
+    _jit_deadline = time.perf_counter() + JIT_DEADLINE_S
     world, rank, local = init_dist(args)
     import torch
     import torch.distributed as dist
@@ -591,9 +643,9 @@ def main(argv=None):
     torch.cuda.synchronize()
     kernel = "bitslice" if lib.rse_get_option(6) > n_bs else "table"
     kernel_id = last_kernel()
-    # correctness gate, every rank on its own stripes, verdicts combined
-    verdict, checked = (check_stripes(v, mine, pool, k, p) if (k, p, L) == (10, 4, 16 * MiB)
-                        else (-1, []))
+    # correctness gate (--full), every rank on its own stripes, verdicts combined
+    verdict, checked = (check_stripes(v, mine, pool, k, p)
+                        if args.full and (k, p, L) == (10, 4, 16 * MiB) else (-1, []))
     verdicts = gather(verdict, world, rank, coll_dev)
     if any(x == 0 for x in verdicts):
         if rank == 0:
@@ -625,12 +677,15 @@ def main(argv=None):
     launches = -(-n_local // pool)
     mean_ms = sum(kern_ms) / len(kern_ms) / launches
     rank_ms = gather(mean_ms, world, rank, coll_dev)
+    if args.dump_outputs:
+        dump_outputs(v, k, p, args.dump_outputs, rank, world)
 
     extras = {}
-    if not args.no_extras:
+    with_extras = args.full and not args.no_extras
+    if with_extras:
         extras["end_to_end_host_all_ranks"] = host_leg(r, v, k, p, L, stream, world, rank,
                                                        coll_dev)
-    if rank == 0 and not args.no_extras and world == 1:  # single-GPU legs
+    if rank == 0 and with_extras and world == 1:  # single-GPU legs
         if (k, p, L) == (10, 4, 16 * MiB):
             # every other leg gets HBM of its own, allocated after the
             # headline's 112 GiB is freed (not the memory left around it)
@@ -639,9 +694,12 @@ def main(argv=None):
             torch.cuda.empty_cache()
             extras.update(fresh_extra_legs(r, k, p, L, min(pool, 256), stream))
             extras["other_configs"] = other_configs(stream)
-            extras["gf16_proper"] = gf16_proper_leg(stream)
             extras["reconstruct_batch_4k"] = batch_leg(stream)
             extras["reference_bench_matrix"] = reference_bench_matrix(stream)
+            # last: on a cold JIT cache its eight chain modules hold every
+            # build thread for many minutes, and the legs above would wait
+            # behind them for modules that build in seconds
+            extras["gf16_proper"] = gf16_proper_leg(stream)
         else:
             extras.update(extra_legs(r, v, k, p, L, min(pool, 256), stream))
         host_agreement(extras)
@@ -662,7 +720,7 @@ def main(argv=None):
                 "kernel_ms_per_launch_min_max": [round(min(rank_ms), 4), round(max(rank_ms), 4)],
                 "algorithmic_bytes_per_launch": int(per_launch_bytes)}
         cpu = {}
-        if world == 1 and not args.no_cpu:
+        if world == 1 and args.full and not args.no_cpu:
             cpu = cpu_baselines(args.cpu_seconds, cpu_threads())
         line = {
             "metric": METRIC, "value": round(value, 1), "unit": "MB/s", "n_gpus": world,
@@ -681,8 +739,8 @@ def main(argv=None):
             "roofline": roof, "cpu_baseline": cpu.get("cpu_baseline"),
         }
         line["library"] = library_info()
-        emit_results(line, cpu, extras, args.full_out or os.path.join(
-            ROOT, "gpurun_out", f"bench_full_n{world}.json"))
+        emit_results(line, cpu, extras, args.full_out or (os.path.join(
+            ROOT, FULL_OUT_DIR, f"bench_full_n{world}.json") if args.full else None))
     if world > 1:
         dist.destroy_process_group()
 
@@ -973,12 +1031,22 @@ GF16_PROPER = (1000, 24, 64 << 10, 512)
 # skipped (RSE_BENCH_JIT_BUDGET_S): with the tree's jitcache/ they load in
 # milliseconds; a cold build of the largest would hold the bench for minutes
 JIT_BUDGET_S = float(os.environ.get("RSE_BENCH_JIT_BUDGET_S", "180"))
+# ... and how long after its start a run may still be waiting for them
+# (RSE_BENCH_JIT_DEADLINE_S; armed by main()): past it a wait is cut to
+# JIT_LOAD_S, enough to load cached modules, so a run on an empty cache ends
+# within minutes with the late legs reported as skipped
+JIT_DEADLINE_S = float(os.environ.get("RSE_BENCH_JIT_DEADLINE_S", "330"))
+JIT_LOAD_S = 5.0
+_jit_deadline = None  # perf_counter() value, or None: no deadline (the legs called on their own)
 
 
 def kernels_within(r, budget_s):
-    """r.kernel_kind(wait=True) if it returns within budget_s, else None (the
-    build goes on in the background; its helpers stop at exit)."""
+    """r.kernel_kind(wait=True) if it returns within budget_s (and, in a
+    bench run, before the run's JIT deadline), else None (the build goes on in
+    the background; its helpers stop at exit)."""
     import threading
+    if _jit_deadline is not None:
+        budget_s = max(JIT_LOAD_S, min(budget_s, _jit_deadline - time.perf_counter()))
     out = []
     th = threading.Thread(target=lambda: out.append(r.kernel_kind(wait=True)), daemon=True)
     th.start()

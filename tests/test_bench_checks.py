@@ -311,3 +311,107 @@ def test_warm_calls_runs_for_the_time_given():
     t0 = time.perf_counter()
     bench.warm_calls(lambda: n.append(1), seconds=0.05)
     assert time.perf_counter() - t0 >= 0.05 and len(n) >= 2
+
+
+def test_jit_waits_end_at_the_run_deadline(monkeypatch):
+    """bench.kernels_within: past the run's JIT deadline a wait for modules
+    that are still building is cut to JIT_LOAD_S and reports None (the leg
+    then says it was skipped), while modules that are there are still used."""
+    import threading
+    done = threading.Event()
+
+    class _Building:
+        def kernel_kind(self, wait):
+            done.wait(30)
+            return "late"
+
+    class _Cached:
+        def kernel_kind(self, wait):
+            return "bitslice-specialised"
+
+    monkeypatch.setattr(bench, "JIT_LOAD_S", 0.02)
+    monkeypatch.setattr(bench, "_jit_deadline", time.perf_counter() - 1.0)
+    t0 = time.perf_counter()
+    try:
+        assert bench.kernels_within(_Building(), 60.0) is None
+    finally:
+        done.set()
+    assert time.perf_counter() - t0 < 5.0
+    assert bench.kernels_within(_Cached(), 60.0) == "bitslice-specialised"
+    monkeypatch.setattr(bench, "_jit_deadline", None)  # a leg called on its own: no deadline
+    assert bench.kernels_within(_Cached(), 0.5) == "bitslice-specialised"
+
+
+# ------------------------------------------------- plain runs, --dump-outputs
+def test_dump_outputs_is_a_fixed_sample_of_the_parity(tmp_path):
+    """bench.dump_outputs on the oracle's stripes: one block of every parity
+    shard of every stripe as float32, the same blocks on every call, each equal
+    to the bytes at its place in the stripe view; past DUMP_LIMIT a subset of
+    the shards, never more bytes than the limit."""
+    v = _stripes()
+    a = np.load(bench.dump_outputs(v, K, P, str(tmp_path / "a"), 0, 1))
+    b = np.load(bench.dump_outputs(v.clone(), K, P, str(tmp_path / "b"), 1, 2))
+    assert (tmp_path / "a" / "parity_sample.npy").exists()
+    assert (tmp_path / "b" / "parity_sample_rank1.npy").exists()
+    assert a.dtype == np.float32 and a.shape == (N * P, L) and np.array_equal(a, b)
+    # L == DUMP_BLOCK here: the whole of every parity shard, in stripe order
+    assert np.array_equal(a.reshape(N, P, L), v[:, K:].numpy().astype(np.float32))
+    # longer shards: a block of each at a seeded offset, found again in the shard
+    w = torch.from_numpy(np.random.default_rng(1).integers(
+        0, 256, (3, K + P, 3 * L + 5), dtype=np.uint8))
+    c = np.load(bench.dump_outputs(w, K, P, str(tmp_path / "c"), 0, 1))
+    offs = np.random.default_rng(bench.SEED).integers(0, w.shape[2] - L + 1, size=3 * P)
+    assert len(set(offs)) > 1
+    for n, off in enumerate(offs):
+        assert np.array_equal(c[n], w[n // P, K + n % P, off:off + L].numpy().astype(np.float32))
+    old = bench.DUMP_LIMIT
+    bench.DUMP_LIMIT = 5 * 4 * L  # room for 5 of the 8 blocks
+    try:
+        d = np.load(bench.dump_outputs(v, K, P, str(tmp_path / "d"), 0, 1))
+    finally:
+        bench.DUMP_LIMIT = old
+    assert d.shape == (5, L) and d.nbytes <= 5 * 4 * L
+    whole = {a[n].tobytes() for n in range(N * P)}
+    assert all(d[n].tobytes() in whole for n in range(5))
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_headline_only_and_dumps_its_parity(tmp_path):
+    """A plain bench.py run (4 stripes, 3 timed steps): the contract keys with
+    `steps` as asked and ms_per_step = the timed region over the steps, no CPU
+    baseline, no extra leg, no digest gate and no results file; the dumped
+    sample equals the oracle's parity of the same columns of the seeded
+    inputs (so every run and build dumps the same bytes)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3",
+           "--warmup", "1", "--stripes", "4", "--dump-outputs", str(tmp_path / "dump")]
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=str(tmp_path))
+    assert out.returncode == 0, out.stderr[-3000:]
+    d = json.loads(out.stdout.rstrip("\n").split("\n")[-1])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["n_gpus"] == 1
+    assert d["metric"] == bench.METRIC and d["unit"] == "MB/s" and d["dtype"] == "u8"
+    assert d["higher_is_better"] is True and d["value"] > 0 and d["ms_per_step"] > 0
+    # value = MiB of 4 stripes per step over ms_per_step, which the line rounds
+    # to 1e-4 ms: within 2e-3 for any step of 0.025 ms or more
+    assert d["value"] == pytest.approx(4 * 14 * 16 / (d["ms_per_step"] * 1e-3), rel=2e-3)
+    assert d["cpu_baseline"] is None and d["full_results"] is None and d["legs"] == {}
+    assert d["config"]["parity_check_vs_reference"] is None
+    assert d["checks"]["flags"] == 0
+    assert os.listdir(tmp_path) == ["dump"]  # nothing else written
+    a = np.load(tmp_path / "dump" / "parity_sample.npy")
+    assert a.dtype == np.float32 and a.shape == (4 * 4, bench.DUMP_BLOCK)
+    k, p, n = 10, 4, 16 << 20
+    offs = np.random.default_rng(bench.SEED).integers(0, n - bench.DUMP_BLOCK + 1, size=4 * p)
+    c = O.Codec(8, k, p)
+    for s in range(4):
+        data = [O.splitmix_bytes(bench.SEED, bench.shard_id(s, i), n) for i in range(k)]
+        for j in range(p):  # byte column x of the parity depends only on column x of the data
+            off = offs[s * p + j]
+            sh = [x[off:off + bench.DUMP_BLOCK].copy() for x in data]
+            sh += [np.zeros(bench.DUMP_BLOCK, np.uint8) for _ in range(p)]
+            c.encode(sh)
+            assert np.array_equal(a[s * p + j], sh[k + j].astype(np.float32)), (s, j)

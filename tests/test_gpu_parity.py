@@ -1467,7 +1467,7 @@ def test_bench_ranks_rehearsal(ranks, extras, tmp_path):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
            f"--nproc-per-node={ranks}", "--master-addr", "127.0.0.1", "--master-port",
            str(29533 + ranks), os.path.join(root, "bench.py"), "--gpus", str(ranks), "--steps",
-           "2", "--warmup", "1", "--stripes", "4", "--no-cpu",
+           "2", "--warmup", "1", "--stripes", "4", "--full", "--no-cpu",
            "--full-out", str(tmp_path / "full.json")] + ([] if extras else ["--no-extras"])
     out = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600, cwd=root)
     assert out.returncode == 0, out.stderr[-3000:]

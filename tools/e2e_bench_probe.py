@@ -81,5 +81,5 @@ bench.batch_leg = lambda stream: {}
 bench.reference_bench_matrix = lambda stream: {}
 
 if __name__ == "__main__":
-    bench.main(["--no-cpu", "--steps", "5", "--warmup", "2",
+    bench.main(["--full", "--no-cpu", "--steps", "5", "--warmup", "2",
                 "--full-out", os.path.join(ROOT, "gpurun_out", "e2e_bench_probe.json")])
