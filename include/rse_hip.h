@@ -106,7 +106,8 @@ int rse_codec_matrix(const rse_codec *codec, uint8_t *out, size_t out_bytes);
 #define RSE_KERNELS_SPECIALISING 3      /* compile in flight (wait == 0) */
 #define RSE_KERNELS_SPECIALISE_FAILED 4 /* compile failed: table kernels */
 #define RSE_KERNELS_FFT 5               /* additive-FFT kernels, compiled into the library
-                                           (GF(2^8) k = p = 16, 32, 64; RSE_OPT_FFT) */
+                                           (GF(2^8) k = p = 16, 32, 64, and 128 at
+                                           RSE_OPT_FFT 2) */
 int rse_codec_kernel_kind(const rse_codec *codec, int wait);
 
 /* encode (core.rs:597-611): shards[0..k] data, shards[k..k+p] parity (overwritten). */

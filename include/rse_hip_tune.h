@@ -108,7 +108,11 @@
                                         (benches/bandwidth.rs's 16+16 .. 64+64) encode, verify and
                                         rebuild all data shards from the parity shards on additive-FFT
                                         kernels ((k/2) log2 k butterflies per transform instead of
-                                        k x p coefficient networks; same bytes); 0: the wide modules */
+                                        k x p coefficient networks; same bytes); 0: the wide modules;
+                                        2: as 1, and k = p = 128 (GF(2^16) 128+128 too: it codes in
+                                        the GF(2^8) subfield) on its own FFT kernel instead of its two
+                                        wide modules, so it needs no run-time module; any other
+                                        nonzero value counts as 1 */
 #define RSE_OPT_HOST_QUEUES 52        /* host pipeline (*_host_flat) streams: 1 (default) the D2H
                                          stream at high priority, on hardware queues no default-
                                          priority stream shares, so the D2H copies never hold up

@@ -273,7 +273,7 @@ int run_job(const Job& j, hipStream_t s) {
       return run_job(g, s);
     }
   }
-  // GF(2^8) k = p = 16 / 32 / 64: the codec's parity rows (encode, verify; also
+  // GF(2^8) k = p = 16 / 32 / 64 (RSE_OPT_FFT 2: and 128): the codec's parity rows (encode, verify; also
   // their own inverse, so all data shards rebuilt from the parity) on the
   // additive-FFT kernels (rse_fft.hip): every whole 2 KiB column (1 KiB shards: all), the
   // rest of every shard below
@@ -761,7 +761,7 @@ void want_bitslice(const rse_codec* c, size_t len_bytes, bool now = false, size_
   c->jit_requested.store(true, std::memory_order_relaxed);
   if (rse::bitslice_compiled(c->kfield, (uint32_t)c->k, (uint32_t)c->p)) return;
   const Rows rows = parity_rows(c);
-  // k = p = 16 / 32 / 64: the compiled additive-FFT kernels (rse_fft.hip)
+  // k = p = 16 / 32 / 64 (RSE_OPT_FFT 2: and 128): the compiled additive-FFT kernels (rse_fft.hip)
   if (rse::fft_applies(c->kfield, (uint32_t)c->k, (uint32_t)c->p, rows.c.data())) return;
   if (wide && rse::wide_eligible((uint32_t)c->k, (uint32_t)c->p))
     rse::jit_register_wide(c->kfield, (uint32_t)c->k, (uint32_t)c->p, rows.c.data(), false);
@@ -1089,7 +1089,7 @@ int run_plan_tail(const rse_codec* c, const ReconPlan& plan, size_t off, uint64_
   return run_job(j, s);
 }
 
-// Every data shard of a k = p = 16 / 32 / 64 GF(2^8) codec rebuilt from its
+// Every data shard of a k = p = 16 / 32 / 64 (RSE_OPT_FFT 2: and 128) GF(2^8) codec rebuilt from its
 // parity shards: run_job codes the plan's rows on the additive-FFT kernels
 // (rse_fft.hip), so neither a pattern module nor the syndrome kernels apply.
 bool fft_plan(const rse_codec* c, const ReconPlan& plan) {

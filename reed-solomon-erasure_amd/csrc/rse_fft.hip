@@ -58,34 +58,10 @@
 #include "rse_bitslice_core.hpp"
 #include "rse_field.hpp"
 #include "rse_fft.hpp"
+#include "rse_fft_sched.hpp"
 
 namespace rse {
 namespace {
-
-// ------------------------------------------------------ field, at compile time
-constexpr uint32_t f8_inv(uint32_t a) {
-  for (uint32_t x = 1; x < 256; ++x)
-    if (hb_mul8(a, x) == 1u) return x;
-  return 0;
-}
-// s_i(x): the subspace polynomial of span(1, 2, .. 2^(i-1)) at x
-constexpr uint32_t fft_vanish(int i, uint32_t x) {
-  uint32_t r = 1;
-  for (uint32_t a = 0; a < (1u << i); ++a) r = hb_mul8(r, x ^ a);
-  return r;
-}
-// s^_i(x) = s_i(x) / s_i(2^i): the butterfly twiddle of level i at shift x
-constexpr uint32_t fft_skew(int i, uint32_t x) {
-  return hb_mul8(fft_vanish(i, x), f8_inv(fft_vanish(i, 1u << i)));
-}
-// Row q of the 8 x 8 bit matrix of multiplication by c: bit j set when bit q
-// of c . 2^j is (the planes of b that plane q of c . b XORs).
-constexpr uint64_t fft_row(uint32_t c, int q) {
-  uint64_t m = 0;
-  for (int j = 0; j < 8; ++j)
-    if ((hb_mul8(c, 1u << j) >> q) & 1u) m |= 1ull << j;
-  return m;
-}
 
 template <uint32_t C, int... Q>
 __device__ __forceinline__ void fft_mul_add(uint32_t (&a)[8], const uint32_t (&b)[8],
@@ -106,84 +82,67 @@ __device__ __forceinline__ void fft_bfly(uint32_t (&a)[8], uint32_t (&b)[8]) {
   }
 }
 
-// Which element register r of a wave holds, and back, by phase.
-//  A / C: wave H holds elements 8H + r.
-template <int H>
-struct MapAC {
-  static constexpr int elem(int r) { return 8 * H + r; }
-  static constexpr int reg(int e) { return e - 8 * H; }
-};
-//  B: the wave's groups of G = K / 8 elements with the same low three bits,
-//  register gi * G + t = element g + 8 t.  Only bits >= 3 matter to the
-//  levels of phase B, so the first wave's map serves every wave.
-template <int K>
-struct MapB {
-  static constexpr int G = K / 8;
-  static constexpr int elem(int r) { return (r / G) + 8 * (r % G); }
-  static constexpr int reg(int e) { return (e & 7) * G + (e >> 3); }
+// The butterflies of the kernels for rse_fft_sched.hpp: an element is 8 planes.
+struct PlaneOps {
+  template <int I, int J, uint32_t C, bool INV>
+  static __device__ __forceinline__ void bfly(uint32_t (&a)[8], uint32_t (&b)[8]) {
+    fft_bfly<C, INV>(a, b);
+  }
 };
 
-// One level I of a transform at shift BETA over the 8 registers: every
-// register whose element has bit I clear is butterflied with its partner.
-template <class M, uint32_t BETA, int I, bool INV, int R = 0>
-__device__ __forceinline__ void fft_level(uint32_t (&x)[8][8]) {
-  if constexpr (R < 8) {
-    constexpr int e = M::elem(R);
-    if constexpr (((e >> I) & 1) == 0) {
-      constexpr int r2 = M::reg(e + (1 << I));
-      constexpr uint32_t c = fft_skew(I, BETA ^ (uint32_t)(e & ~((2 << I) - 1)));
-      fft_bfly<c, INV>(x[R], x[r2]);
+// A workgroup's columns: column c's byte offset for this lane, the stripe it
+// belongs to, and whether that stripe exists (SUB: the last column of an odd
+// stripe count loads its last stripe twice and stores it once).
+template <uint32_t SUB>
+struct FftCols {
+  static constexpr uint32_t S = SUB ? SUB / 2u : 1024u;  // a lane's two vectors, S apart
+  static constexpr uint32_t SPC = 2048u / (SUB ? SUB : 2048u), LPS = 64u / SPC;  // stripes / column, lanes / stripe
+  uint64_t cols, total, stripe_stride;
+  uint32_t n_stripes, lane, lane_off;
+  template <class A>
+  __device__ __forceinline__ FftCols(const A& a)
+      : cols(a.cols_per_stripe),
+        total(SUB ? ((uint64_t)a.n_stripes + SPC - 1) / SPC : a.cols_per_stripe * a.n_stripes),
+        stripe_stride(a.stripe_stride),
+        n_stripes(a.n_stripes),
+        lane(threadIdx.x & 63u),
+        lane_off((SUB ? (threadIdx.x & 63u) % LPS : (threadIdx.x & 63u)) * 16u) {}
+  __device__ __forceinline__ uint64_t stripe(uint64_t c) const {
+    return SUB ? c * SPC + lane / LPS : c / cols;
+  }
+  __device__ __forceinline__ bool ok(uint64_t c) const { return SUB == 0 || stripe(c) < n_stripes; }
+  __device__ __forceinline__ uint64_t off(uint64_t c) const {
+    if constexpr (SUB) {
+      uint64_t s = stripe(c);
+      if (s >= n_stripes) s = n_stripes - 1;  // loaded, never stored
+      return s * stripe_stride + lane_off;
     }
-    fft_level<M, BETA, I, INV, R + 1>(x);
+    const uint64_t s = c / cols;
+    return s * stripe_stride + (c - s * cols) * 2048u + lane_off;
   }
-}
+};
 
-// Phase A of wave H: the inverse transform at B0, levels 0-2.
-template <int H, uint32_t B0>
-__device__ __forceinline__ void fft_phase_a(uint32_t (&x)[8][8]) {
-  fft_level<MapAC<H>, B0, 0, true>(x);
-  fft_level<MapAC<H>, B0, 1, true>(x);
-  fft_level<MapAC<H>, B0, 2, true>(x);
-}
-// Phase C of wave H: the forward transform at B1, levels 2-0.
-template <int H, uint32_t B1>
-__device__ __forceinline__ void fft_phase_c(uint32_t (&x)[8][8]) {
-  fft_level<MapAC<H>, B1, 2, false>(x);
-  fft_level<MapAC<H>, B1, 1, false>(x);
-  fft_level<MapAC<H>, B1, 0, false>(x);
-}
-// Phase B: the inverse transform's levels 3 .. m-1 at B0, then the forward
-// transform's levels m-1 .. 3 at B1.
-template <int K, uint32_t B0, uint32_t B1, int I>
-__device__ __forceinline__ void fft_phase_b_inv(uint32_t (&x)[8][8]) {
-  if constexpr ((1 << I) < K) {
-    fft_level<MapB<K>, B0, I, true>(x);
-    fft_phase_b_inv<K, B0, B1, I + 1>(x);
+// A wave's outputs T0 .. T1-1 of its E of column c (elements e0 ..): un-sliced,
+// then stored and / or compared by mode.  True when a compared vector differs.
+template <int E, uint32_t SUB, int T0 = 0, int T1 = E, class A>
+__device__ __forceinline__ bool fft_emit(const A& a, const FftCols<SUB>& fc, uint32_t (&x)[E][8],
+                                         int e0, uint64_t off, bool ok, uint32_t mode) {
+  bool d = false;
+#pragma unroll
+  for (int t = T0; t < T1; ++t) {
+    u32x4 v[2];
+    unslice8(x[t], v);
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const uint64_t o16 = off + j * FftCols<SUB>::S;
+      if (mode != kCheck && ok) stv<true>(a.out[e0 + t] + o16, v[j]);
+      if (mode != kStore) {
+        const u32x4 q = ldv<true>(a.cmp[e0 + t] + o16);
+        d |= ok & ((q.x != v[j].x) | (q.y != v[j].y) | (q.z != v[j].z) | (q.w != v[j].w));
+      }
+    }
   }
-}
-template <int K, uint32_t B1, int I>
-__device__ __forceinline__ void fft_phase_b_fwd(uint32_t (&x)[8][8]) {
-  if constexpr (I >= 3) {
-    fft_level<MapB<K>, B1, I, false>(x);
-    fft_phase_b_fwd<K, B1, I - 1>(x);
-  }
-}
-constexpr int fft_log2(int k) { return k <= 1 ? 0 : 1 + fft_log2(k / 2); }
-
-// The wave-dependent phases, dispatched on the (uniform) wave index.
-template <int K, uint32_t B0, int H = 0>
-__device__ __forceinline__ void fft_a(int w, uint32_t (&x)[8][8]) {
-  if constexpr (H < K / 8) {
-    if (w == H) fft_phase_a<H, B0>(x);
-    else fft_a<K, B0, H + 1>(w, x);
-  }
-}
-template <int K, uint32_t B1, int H = 0>
-__device__ __forceinline__ void fft_c(int w, uint32_t (&x)[8][8]) {
-  if constexpr (H < K / 8) {
-    if (w == H) fft_phase_c<H, B1>(x);
-    else fft_c<K, B1, H + 1>(w, x);
-  }
+  return d;
 }
 
 // LDS: element e's 8 planes, as two quads of planes per lane.
@@ -206,86 +165,59 @@ __device__ __forceinline__ void fft_get(const uint4 (&slot)[2][64], uint32_t (&x
   x[7] = b.w;
 }
 
-// The kernel: K = k = p, B0 / B1 the cosets of the inputs / outputs (0 / K:
-// the parity rows, which are also their inverse), SUB 1024 for 1 KiB shards
-// (two stripes per 2 KiB column), else 0 (whole 2 KiB columns).
+// The kernel of K = k = p <= 64: B0 / B1 the cosets of the inputs / outputs
+// (0 / K: the parity rows, which are also their inverse), SUB 1024 for 1 KiB
+// shards (two stripes per 2 KiB column), else 0 (whole 2 KiB columns).
 template <int K, uint32_t B0, uint32_t B1, uint32_t SUB>
-__global__ __launch_bounds__(K * 8) void fft_kernel(const FftArgs a) {
+__global__ __launch_bounds__(K * 8) void fft_kernel(const FftArgs<K> a) {
   static_assert(K == 16 || K == 32 || K == 64, "k = p = 16, 32 or 64");
+  using SC = FftSched<K>;
+  static_assert(SC::E == 8 && SC::W * 64 == K * 8, "8 elements per wave");
   __shared__ FftPlanes<K> st;
-  constexpr int G = K / 8;         // phase B: elements per group
-  constexpr int GPW = 8 / G;       // ... groups per wave
-  constexpr uint32_t S = SUB ? SUB / 2u : 1024u;            // a lane's two vectors, S apart
-  constexpr uint32_t SPC = 2048u / (SUB ? SUB : 2048u), LPS = 64u / SPC;  // stripes / column, lanes / stripe
+  constexpr uint32_t S = FftCols<SUB>::S;
   const int w = (int)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t lane_off = (SUB ? lane % LPS : lane) * 16u;
-  const uint64_t cols = a.cols_per_stripe;
-  const uint64_t total = SUB ? (a.n_stripes + SPC - 1) / SPC : cols * a.n_stripes;
+  const FftCols<SUB> fc(a);
+  const uint32_t lane = fc.lane;
+  const uint64_t total = fc.total;
   const uint32_t mode = a.mode;
-  auto col_off = [&](uint64_t c) {
-    if constexpr (SUB) {
-      uint64_t stripe = c * SPC + lane / LPS;
-      if (stripe >= a.n_stripes) stripe = a.n_stripes - 1;  // loaded, never stored
-      return stripe * a.stripe_stride + lane_off;
-    }
-    const uint64_t stripe = c / cols;
-    return stripe * a.stripe_stride + (c - stripe * cols) * 2048u + lane_off;
-  };
   const uint8_t* const* in = a.in + 8 * w;
   u32x4 buf[8][2];
   if (blockIdx.x < total) {
-    const uint64_t off0 = col_off(blockIdx.x);
+    const uint64_t off0 = fc.off(blockIdx.x);
 #pragma unroll
     for (int t = 0; t < 8; ++t) load2<S>(buf[t], in[t] + off0);
   }
   bool diff = false;
   for (uint64_t c = blockIdx.x; c < total; c += gridDim.x) {
-    const uint64_t off = col_off(c);
+    const uint64_t off = fc.off(c);
     const uint64_t next = c + gridDim.x;
     uint32_t x[8][8];
 #pragma unroll
     for (int t = 0; t < 8; ++t) slice8(buf[t], x[t]);
     if (next < total) {  // the next column's inputs in flight through the transform
-      const uint64_t noff = col_off(next);
+      const uint64_t noff = fc.off(next);
 #pragma unroll
       for (int t = 0; t < 8; ++t) load2<S>(buf[t], in[t] + noff);
     }
     // phase A, then its results into the slots this wave read in phase C
-    fft_a<K, B0>(w, x);
+    fft_a<PlaneOps, K, B0, 0, SC::LA, 0, 8>(w, x);
 #pragma unroll
-    for (int t = 0; t < 8; ++t) fft_put(st[8 * w + t], x[t], lane);
+    for (int t = 0; t < 8; ++t) fft_put(st[SC::ac_slot(w, t)], x[t], lane);
     __syncthreads();
     // phase B on this wave's groups (the same slots written back)
 #pragma unroll
-    for (int r = 0; r < 8; ++r) fft_get(st[(w * GPW + r / G) + 8 * (r % G)], x[r], lane);
-    fft_phase_b_inv<K, B0, B1, 3>(x);
-    fft_phase_b_fwd<K, B1, fft_log2(K) - 1>(x);
+    for (int r = 0; r < 8; ++r) fft_get(st[SC::b_slot(w, r)], x[r], lane);
+    fft_phase_b<PlaneOps, K, B0, B1>(x);
 #pragma unroll
-    for (int r = 0; r < 8; ++r) fft_put(st[(w * GPW + r / G) + 8 * (r % G)], x[r], lane);
+    for (int r = 0; r < 8; ++r) fft_put(st[SC::b_slot(w, r)], x[r], lane);
     __syncthreads();
     // phase C on this wave's own elements, then its 8 outputs
 #pragma unroll
-    for (int t = 0; t < 8; ++t) fft_get(st[8 * w + t], x[t], lane);
-    fft_c<K, B1>(w, x);
-    const bool ok = SUB == 0 || c * SPC + lane / LPS < a.n_stripes;
-    bool d = false;
-#pragma unroll
-    for (int t = 0; t < 8; ++t) {
-      u32x4 v[2];
-      unslice8(x[t], v);
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const uint64_t o16 = off + j * S;
-        if (mode != kCheck && ok) stv<true>(a.out[8 * w + t] + o16, v[j]);
-        if (mode != kStore) {
-          const u32x4 q = ldv<true>(a.cmp[8 * w + t] + o16);
-          d |= ok & ((q.x != v[j].x) | (q.y != v[j].y) | (q.z != v[j].z) | (q.w != v[j].w));
-        }
-      }
-    }
+    for (int t = 0; t < 8; ++t) fft_get(st[SC::ac_slot(w, t)], x[t], lane);
+    fft_c<PlaneOps, K, B1>(w, x);
+    const bool d = fft_emit<8, SUB>(a, fc, x, 8 * w, off, fc.ok(c), mode);
     if (a.per_stripe) {
-      if (d) flag_mismatch(a.mismatch + (SUB ? c * SPC + lane / LPS : c / cols));
+      if (d) flag_mismatch(a.mismatch + fc.stripe(c));
     } else {
       diff |= d;
     }
@@ -293,43 +225,215 @@ __global__ __launch_bounds__(K * 8) void fft_kernel(const FftArgs a) {
   if (mode != kStore && diff) flag_mismatch(a.mismatch);
 }
 
+// The kernel of K = k = p = 128: 8 waves of 16 elements (x[16][8]: 128 VGPRs,
+// two waves per SIMD).  128 elements x 2 KiB do not fit a CU's 160 KiB of LDS,
+// so each of the two exchanges goes one quad of planes at a time through
+// 128 elements x 4 planes x 64 lanes x 4 B = 128 KiB: a wave puts planes 0-3
+// of its registers, takes planes 0-3 of the other phase's elements into the
+// registers just freed, and then the same for planes 4-7.  A wave puts its
+// phase-B results into the slots it took them from and its phase-A results
+// into the slots it takes in phase C, so only the puts of planes 4-7 have to
+// wait for the other waves' takes of planes 0-3: six barriers per column.
+// The next column's 16 inputs would be another 128 VGPRs, so the inputs arrive
+// by quarters (rse_fft_sched.hpp fft_phase_a_quarters): four elements in
+// flight while phase A runs on the ones before, the next column's first four
+// while the last twelve outputs are un-sliced and stored (in flight through
+// the whole transform they cost 32 VGPRs the kernel does not have).  Wave H's whole column loop is its own copy of the
+// code (fft_for_wave in the kernel): with the wave's branch inside the loop,
+// around phases A and C as in fft_kernel, the register allocator spilled 400+
+// bytes per lane around the branches.
+using FftQuads = uint32_t[128][4][64];  // a quad of planes of element e: [plane][lane]
+
+template <int K, uint32_t B0, uint32_t B1, uint32_t SUB, int H>
+__device__ __forceinline__ void fft_quads_wave(const FftArgs<K>& a, FftQuads& st) {
+  using SC = FftSched<K>;
+  constexpr int E = SC::E, QN = E / 4;
+  constexpr uint32_t S = FftCols<SUB>::S;
+  const FftCols<SUB> fc(a);
+  const uint32_t lane = fc.lane;
+  const uint64_t total = fc.total;
+  const uint32_t mode = a.mode;
+  const uint8_t* const* in = a.in + E * H;
+  u32x4 buf[QN][2];
+  if (blockIdx.x < total) {
+    const uint64_t off0 = fc.off(blockIdx.x);
+#pragma unroll
+    for (int t = 0; t < QN; ++t) load2<S>(buf[t], in[t] + off0);
+  }
+  // planes 4 Q .. 4 Q + 3 of the wave's registers to / from its slots
+  auto put = [&](uint32_t (&x)[E][8], auto q, auto phase_b) {
+    constexpr int Q = decltype(q)::value;
+#pragma unroll
+    for (int r = 0; r < E; ++r)
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        st[decltype(phase_b)::value ? SC::b_slot(H, r) : SC::ac_slot(H, r)][j][lane] = x[r][4 * Q + j];
+  };
+  auto take = [&](uint32_t (&x)[E][8], auto q, auto phase_b) {
+    constexpr int Q = decltype(q)::value;
+#pragma unroll
+    for (int r = 0; r < E; ++r)
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        x[r][4 * Q + j] = st[decltype(phase_b)::value ? SC::b_slot(H, r) : SC::ac_slot(H, r)][j][lane];
+  };
+  using Q0 = FftConst<0>;
+  using Q1 = FftConst<1>;
+  using AC = FftConst<0>;
+  using B = FftConst<1>;
+  bool diff = false;
+  for (uint64_t c = blockIdx.x; c < total; c += gridDim.x) {
+    const uint64_t off = fc.off(c);
+    const uint64_t next = c + gridDim.x;
+    uint32_t x[E][8];
+    // phase A, a quarter of the inputs in flight at a time
+    fft_phase_a_quarters<PlaneOps, K, H, B0>(x, [&](auto q) {
+      constexpr int Q = decltype(q)::value;
+      // (the scheduler otherwise issues all sixteen loads at once: 96 more VGPRs)
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int t = 0; t < QN; ++t) slice8(buf[t], x[QN * Q + t]);
+      if constexpr (Q < 3) {
+#pragma unroll
+        for (int t = 0; t < QN; ++t) load2<S>(buf[t], in[QN * (Q + 1) + t] + off);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    });
+    // to this wave's phase-B groups
+    put(x, Q0{}, AC{});
+    __syncthreads();
+    take(x, Q0{}, B{});
+    __syncthreads();
+    put(x, Q1{}, AC{});
+    __syncthreads();
+    take(x, Q1{}, B{});
+    fft_phase_b<PlaneOps, K, B0, B1>(x);
+    // and back to its own elements
+    put(x, Q0{}, B{});
+    __syncthreads();
+    take(x, Q0{}, AC{});
+    __syncthreads();
+    put(x, Q1{}, B{});
+    __syncthreads();
+    take(x, Q1{}, AC{});
+    fft_phase_c<PlaneOps, E, H, B1, SC::LA - 1>(x);
+    // the first outputs free the registers of the next column's first inputs
+    __builtin_amdgcn_sched_barrier(0);
+    bool d = fft_emit<E, SUB, 0, QN>(a, fc, x, E * H, off, fc.ok(c), mode);
+    if (next < total) {
+      const uint64_t noff = fc.off(next);
+#pragma unroll
+      for (int t = 0; t < QN; ++t) load2<S>(buf[t], in[t] + noff);
+    }
+    d |= fft_emit<E, SUB, QN, E>(a, fc, x, E * H, off, fc.ok(c), mode);
+    if (a.per_stripe) {
+      if (d) flag_mismatch(a.mismatch + fc.stripe(c));
+    } else {
+      diff |= d;
+    }
+  }
+  if (mode != kStore && diff) flag_mismatch(a.mismatch);
+}
+
+template <int K, uint32_t B0, uint32_t B1, uint32_t SUB>
+__global__ __launch_bounds__(512) void fft_kernel_quads(const FftArgs<K> a) {
+  static_assert(K == 128, "k = p = 128");
+  using SC = FftSched<K>;
+  static_assert(SC::E == 16 && SC::W == 8 && SC::LA == 4, "8 waves of 16 elements");
+  static_assert(sizeof(FftQuads) == sizeof(uint32_t) * K * 4 * 64 && sizeof(FftQuads) <= 160 * 1024, "LDS");
+  __shared__ FftQuads st;
+  const int w = (int)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  fft_for_wave<K>(w, [&](auto h) { fft_quads_wave<K, B0, B1, SUB, decltype(h)::value>(a, st); });
+}
+
 // ------------------------------------------------------------------- host
 // The rows the kernels replace: the K+K codec's parity rows (encode, verify;
 // their own inverse, so also every data shard rebuilt from the parity shards
 // in parity order: reconstruct with shards 0 .. K-1 missing, core.rs:801-923).
-struct FftRows {
-  std::vector<uint16_t> par[3];  // K = 16, 32, 64
-};
-const FftRows& fft_rows() {
-  static const FftRows r = [] {
-    FftRows f;
-    for (int q = 0; q < 3; ++q) {
-      const size_t K = 16u << q;
-      const Matrix<Gf8Field> v = Matrix<Gf8Field>::vandermonde(2 * K, K);
-      Matrix<Gf8Field> top(K, K), inv;
-      for (size_t i = 0; i < K; ++i)
-        for (size_t j = 0; j < K; ++j) top.at(i, j) = v.at(i, j);
-      top.invert(inv);
-      const Matrix<Gf8Field> m = v.multiply(inv);  // core.rs:430-436
-      f.par[q].assign(m.d.begin() + K * K, m.d.begin() + 2 * K * K);
-    }
-    return f;
+// Built on K's first use: a 16+16 caller does not pay for the 128 x 128
+// inversion.
+template <size_t K>
+const std::vector<uint16_t>& fft_rows() {
+  static const std::vector<uint16_t> r = [] {
+    const Matrix<Gf8Field> v = Matrix<Gf8Field>::vandermonde(2 * K, K);
+    Matrix<Gf8Field> top(K, K), inv;
+    for (size_t i = 0; i < K; ++i)
+      for (size_t j = 0; j < K; ++j) top.at(i, j) = v.at(i, j);
+    top.invert(inv);
+    const Matrix<Gf8Field> m = v.multiply(inv);  // core.rs:430-436
+    return std::vector<uint16_t>(m.d.begin() + K * K, m.d.begin() + 2 * K * K);
   }();
   return r;
 }
 
+// The kernel of K (its workgroup: FftSched<K>::W waves) and its arguments.
 template <int K>
 const void* fft_fn(uint32_t sub) {
-  return sub ? reinterpret_cast<const void*>(&fft_kernel<K, 0u, K, 1024u>)
-             : reinterpret_cast<const void*>(&fft_kernel<K, 0u, K, 0u>);
+  if constexpr (K == 128)
+    return sub ? reinterpret_cast<const void*>(&fft_kernel_quads<K, 0u, K, 1024u>)
+               : reinterpret_cast<const void*>(&fft_kernel_quads<K, 0u, K, 0u>);
+  else
+    return sub ? reinterpret_cast<const void*>(&fft_kernel<K, 0u, K, 1024u>)
+               : reinterpret_cast<const void*>(&fft_kernel<K, 0u, K, 0u>);
+}
+struct FftLaunch {
+  uint64_t stripe_stride, cols;
+  uint32_t* mismatch;
+  uint32_t n_stripes, mode, per_stripe, sub;
+  const uint8_t* const* in;
+  uint8_t* const* out;
+  const uint8_t* const* cmp;
+  hipStream_t stream;
+};
+template <int K>
+hipError_t fft_launch(const FftLaunch& l) {
+  FftArgs<K> a;
+  std::memset(&a, 0, sizeof a);
+  a.stripe_stride = l.stripe_stride;
+  a.cols_per_stripe = l.cols;
+  a.mismatch = l.mismatch;
+  a.n_stripes = l.n_stripes;
+  a.mode = l.mode;
+  a.per_stripe = l.per_stripe;
+  for (int i = 0; i < K; ++i) {
+    a.in[i] = l.in[i];
+    a.out[i] = l.out ? l.out[i] : nullptr;
+    a.cmp[i] = l.cmp ? l.cmp[i] : nullptr;
+  }
+  const void* fn = fft_fn<K>(l.sub);
+  constexpr uint32_t threads = FftSched<K>::W * 64u;
+  const uint64_t total = l.sub ? ((uint64_t)l.n_stripes + 1) / 2 : l.cols * l.n_stripes;
+  // resident workgroups (LDS: k x 2 KiB each, 128+128: 128 KiB), a few rounds of them
+  int dev = 0, n_cu = 0, per = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e == hipSuccess) e = hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev);
+  if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, fn, threads, 0);
+  if (e != hipSuccess) return e;
+  const int64_t grid_opt = get_option(2);
+  uint64_t gx = grid_opt > 0 ? (uint64_t)grid_opt : (uint64_t)std::max(per, 1) * (uint64_t)n_cu;
+  if (gx > total) gx = total;
+  if (gx > 0x7fffffffu) gx = 0x7fffffffu;
+  void* args[] = {&a};
+  return hipLaunchKernel(fn, dim3((uint32_t)gx), dim3(threads), args, 0, l.stream);
 }
 
 }  // namespace
 
 bool fft_applies(int field, uint32_t k, uint32_t p, const uint16_t* rows) {
-  if (field != 8 || k != p || (k != 16 && k != 32 && k != 64) || !get_option(51)) return false;
-  const int q = k == 16 ? 0 : k == 32 ? 1 : 2;
-  return std::memcmp(rows, fft_rows().par[q].data(), (size_t)k * k * sizeof(uint16_t)) == 0;
+  const int64_t opt = get_option(51);
+  if (field != 8 || k != p || !opt) return false;
+  const std::vector<uint16_t>* par = nullptr;
+  switch (k) {
+    case 16: par = &fft_rows<16>(); break;
+    case 32: par = &fft_rows<32>(); break;
+    case 64: par = &fft_rows<64>(); break;
+    case 128:
+      if (opt < 2) return false;
+      par = &fft_rows<128>();
+      break;
+    default: return false;
+  }
+  return std::memcmp(rows, par->data(), (size_t)k * k * sizeof(uint16_t)) == 0;
 }
 
 hipError_t launch_fft(int field, uint32_t k, uint32_t p, const uint16_t* rows,
@@ -342,39 +446,16 @@ hipError_t launch_fft(int field, uint32_t k, uint32_t p, const uint16_t* rows,
   const uint32_t sub = len == 1024u && get_option(33) != 0 ? 1024u : 0u;
   const uint64_t cols = len / 2048u;
   if (!sub && cols == 0) return hipSuccess;
-  FftArgs a;
-  std::memset(&a, 0, sizeof a);
-  a.stripe_stride = stripe_stride;
-  a.cols_per_stripe = cols;
-  a.mismatch = mismatch;
-  a.n_stripes = n_stripes;
-  a.mode = mode;
-  a.per_stripe = per_stripe ? 1u : 0u;
-  for (uint32_t i = 0; i < k; ++i) {
-    a.in[i] = in[i];
-    a.out[i] = out ? out[i] : nullptr;
-    a.cmp[i] = cmp ? cmp[i] : nullptr;
-  }
-  const void* fn = nullptr;
+  const FftLaunch l{stripe_stride, cols, mismatch, n_stripes, mode, per_stripe ? 1u : 0u, sub,
+                    in, out, cmp, stream};
+  hipError_t e = hipSuccess;
   switch (k) {
-    case 16: fn = fft_fn<16>(sub); break;
-    case 32: fn = fft_fn<32>(sub); break;
-    case 64: fn = fft_fn<64>(sub); break;
+    case 16: e = fft_launch<16>(l); break;
+    case 32: e = fft_launch<32>(l); break;
+    case 64: e = fft_launch<64>(l); break;
+    case 128: e = fft_launch<128>(l); break;
     default: return hipSuccess;
   }
-  const uint64_t total = sub ? ((uint64_t)n_stripes + 1) / 2 : cols * n_stripes;
-  // resident workgroups (LDS: k x 2 KiB each), a few rounds of them
-  int dev = 0, n_cu = 0, per = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e == hipSuccess) e = hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev);
-  if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, fn, k * 8, 0);
-  if (e != hipSuccess) return e;
-  const int64_t grid_opt = get_option(2);
-  uint64_t gx = grid_opt > 0 ? (uint64_t)grid_opt : (uint64_t)std::max(per, 1) * (uint64_t)n_cu;
-  if (gx > total) gx = total;
-  if (gx > 0x7fffffffu) gx = 0x7fffffffu;
-  void* args[] = {&a};
-  e = hipLaunchKernel(fn, dim3((uint32_t)gx), dim3(k * 8), args, 0, stream);
   if (e != hipSuccess) return e;
   note_kernel("fft gf8 %u+%u %s%s", k, p, mode == kStore ? "code" : "check", sub ? " sub1" : "");
   count_bitslice_launch();

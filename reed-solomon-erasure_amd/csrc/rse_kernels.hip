@@ -807,7 +807,7 @@ struct Options {
   int64_t dispatch_lane_units = 1;  // dispatcher: (vector, output) units per lane per workgroup
   int64_t sub_depth = 4;  // narrow modules' 1 / 2 KiB-shard kernels: inputs in flight per wave
   int64_t tune_nosync = 0;  // RSE_TUNE_SPLITS builds: wide modules without barriers (timing)
-  int64_t fft = 1;  // GF(2^8) k = p = 16 / 32 / 64 codecs on the additive-FFT kernels (rse_fft.hip)
+  int64_t fft = 1;  // GF(2^8) k = p = 16 / 32 / 64 (2: and 128) codecs on the additive-FFT kernels (rse_fft.hip)
   int64_t host_queues = 1;  // host pipeline: 1 the D2H stream at high priority, 0 plain (A/B)
   int64_t host_zc_out = 1;  // host pipeline: outputs stored in place in mapped pinned memory
 };
@@ -1358,7 +1358,7 @@ int set_option(int key, int64_t value) {
     case 46: g_opt.wide_block_inputs = value < 0 ? 0 : value; return 0;
     case 49: g_opt.dispatch_lane_units = value < 1 ? 1 : value > 64 ? 64 : value; return 0;
     case 50: g_opt.sub_depth = value < 1 ? 1 : value > 4 ? 4 : value; return 0;
-    case 51: g_opt.fft = value ? 1 : 0; return 0;
+    case 51: g_opt.fft = value == 0 || value == 2 ? value : 1; return 0;
     case 52: g_opt.host_queues = value ? 1 : 0; return 0;
     case 53: g_opt.host_zc_out = value ? 1 : 0; return 0;
 #ifdef RSE_TUNE_SPLITS
