@@ -107,7 +107,8 @@ int rse_codec_matrix(const rse_codec *codec, uint8_t *out, size_t out_bytes);
 #define RSE_KERNELS_SPECIALISE_FAILED 4 /* compile failed: table kernels */
 #define RSE_KERNELS_FFT 5               /* additive-FFT kernels, compiled into the library
                                            (GF(2^8) k = p = 16, 32, 64, and 128 at
-                                           RSE_OPT_FFT 2) */
+                                           RSE_OPT_FFT 2; at RSE_OPT_FFT16 1, GF(2^16)
+                                           codecs past 256 shards with 2^m - k <= 32) */
 int rse_codec_kernel_kind(const rse_codec *codec, int wait);
 
 /* encode (core.rs:597-611): shards[0..k] data, shards[k..k+p] parity (overwritten). */

@@ -122,5 +122,12 @@
                                          the shards an encode or reconstruct writes, when they are
                                          pinned device-mapped host memory, are stored in place by
                                          the kernel (no D2H copies); 0 D2H copies from the ring */
+#define RSE_OPT_FFT16 54              /* 0 (default): off; 1: every GF(2^16) codec past 256 shards
+                                         (coefficients outside the GF(2^8) subfield) with
+                                         2^m - k <= 32, 2^m the smallest power of two >= k + p
+                                         (1000+24, 500+12, 490+12, 2040+8, 4080+16 ...), encodes,
+                                         verifies and reconstructs on one compiled pruned additive-FFT
+                                         kernel with run-time tables (rse_fft16.hip; same bytes):
+                                         usable at once, no run-time module is built or requested */
 
 #endif /* RSE_HIP_TUNE_H */

@@ -30,6 +30,7 @@
 #include "../../include/rse_hip_tune.h"
 #include "rse_dispatch.hpp"
 #include "rse_fft.hpp"
+#include "rse_fft16.hpp"
 #include "rse_wideblk.hpp"
 #include "rse_field.hpp"
 #include "rse_kernels.hpp"
@@ -310,6 +311,31 @@ int run_job(const Job& j, hipStream_t s) {
       RSE_HIP(rse::launch_wide(j.field, (uint32_t)n_in, (uint32_t)n_out, j.rows->c.data(), j.in,
                                j.out, j.cmp, j.len_bytes, j.stripe_stride, (uint32_t)j.n_stripes,
                                j.mode, j.mismatch, j.per_stripe, s, &done));
+    if (done) return done == j.len_bytes ? RSE_OK : run_rest(j, done, s);
+  }
+  // RSE_OPT_FFT16: a GF(2^16) codec past 256 shards with 2^m - k <= 32, its
+  // parity rows (encode, verify) on the pruned-FFT kernel (rse_fft16.hip):
+  // every whole 4 KiB column, the rest of every shard below
+  if (!j.accumulate && j.field == RSE_FIELD_GF16 && j.len_bytes >= 4096 &&
+      j.stripe_stride % 16u == 0 && rse::get_option(RSE_OPT_BITSLICE) &&
+      j.n_stripes <= 0xffffffffu &&
+      rse::fft16_applies(16, (uint32_t)n_in, (uint32_t)n_out, j.rows->c.data())) {
+    bool al = true;
+    for (size_t i = 0; i < n_in; ++i) al = al && aligned16(j.in[i]);
+    for (size_t r = 0; r < n_out; ++r) {
+      if (j.mode != rse::kCheck) al = al && aligned16(j.out[r]);
+      if (j.mode != rse::kStore) al = al && aligned16(j.cmp[r]);
+    }
+    uint64_t done = 0;
+    if (al) {
+      const rse::Fft16Plan* fp = rse::fft16_plan(16, (uint32_t)n_in, (uint32_t)n_out);
+      std::vector<const uint8_t*> in(fp->n, nullptr);
+      std::copy(j.in, j.in + n_in, in.begin());
+      RSE_HIP(rse::launch_fft16(*fp, in.data(), (uint32_t)n_out, fp->enc.data(), j.out, j.cmp,
+                                j.len_bytes, j.stripe_stride, (uint32_t)j.n_stripes, j.mode,
+                                j.mismatch, j.per_stripe, j.mode == rse::kStore ? "code" : "check",
+                                s, &done));
+    }
     if (done) return done == j.len_bytes ? RSE_OK : run_rest(j, done, s);
   }
   // too wide for one module (GF(2^16) past 256 shards): the chain of wide
@@ -752,6 +778,9 @@ hipError_t plan_consts(const rse_codec* c, int dev, const uint8_t** out) {
 constexpr uint64_t kWideJitBytes = 1ull << 30;
 void want_bitslice(const rse_codec* c, size_t len_bytes, bool now = false, size_t n_stripes = 1) {
   if (!bitslice_len(len_bytes) || c->jit_requested.load(std::memory_order_relaxed)) return;
+  // RSE_OPT_FFT16: the compiled pruned-FFT kernel (rse_fft16.hip) codes this
+  // codec, so no module is built (nor requested: the option may be cleared later)
+  if (rse::fft16_plan(c->kfield, (uint32_t)c->k, (uint32_t)c->p)) return;
   const bool wide = c->k > (size_t)kMaxIn || c->p > rse::kJitMaxOut ||
                     rse::wide_eligible((uint32_t)c->k, (uint32_t)c->p);
   if (wide && !now && rse::get_option(RSE_OPT_JIT) < 2) {
@@ -833,10 +862,19 @@ struct ReconPlan {
   size_t len = 0;  // elements
   bool nothing_to_do = false;
   uint32_t pattern_uses = 0;  // decode_matrix *uses
+  // RSE_OPT_FFT16 (rse_fft16.hip): the codec's plan, the n shard pointers the
+  // kernel reads (null outside the k valid ones) and the pattern with its
+  // u-column rows; `rows` has its sizes only, its coefficients (the same map
+  // over the valid inputs, from the plan's tables: no k x k inversion) are
+  // made when bytes are left for the table kernels (run_fft16_plan)
+  const rse::Fft16Plan* fft16 = nullptr;
+  std::vector<const uint8_t*> fft16_in;
+  rse::Fft16Pattern fft16_pattern;
 };
 
 int plan_reconstruct(const rse_codec* c, void* const* shards, const size_t* lens,
-                     const uint8_t* present, size_t n, bool data_only, ReconPlan& plan) {
+                     const uint8_t* present, size_t n, bool data_only, ReconPlan& plan,
+                     bool fft16 = false) {
   int rc = check_count(n, c->total, RSE_TOO_FEW_SHARDS, RSE_TOO_MANY_SHARDS);
   if (rc) return rc;
   if (!lens || !present) return RSE_ERR_INVALID_ARGUMENT;
@@ -879,6 +917,25 @@ int plan_reconstruct(const rse_codec* c, void* const* shards, const size_t* lens
   }
   for (size_t v : valid)
     if (!shards[v]) return RSE_ERR_INVALID_ARGUMENT;
+
+  if (const rse::Fft16Plan* fp =
+          fft16 ? rse::fft16_plan(c->kfield, (uint32_t)k, (uint32_t)c->p) : nullptr) {
+    // the valid shards S are the first k present ones, as above; the plan's
+    // one u x u inversion gives every lost shard from the top u coefficients
+    rse::Fft16Pattern pt;
+    if (!rse::fft16_pattern(*fp, present, data_only, pt)) return RSE_ERR_SINGULAR_MATRIX;  // unreachable
+    plan.fft16 = fp;
+    plan.fft16_in.assign(fp->n, nullptr);
+    for (uint32_t v : pt.valid) plan.fft16_in[v] = static_cast<const uint8_t*>(shards[v]);
+    plan.rows.n_in = k;
+    plan.rows.n_out = pt.lost.size();
+    for (uint32_t q : pt.lost) plan.out.push_back(static_cast<uint8_t*>(shards[q]));
+    plan.fft16_pattern = std::move(pt);
+    for (size_t v : valid) plan.in.push_back(static_cast<const uint8_t*>(shards[v]));
+    plan.len = shard_len;
+    plan.pattern_uses = 1;
+    return RSE_OK;
+  }
 
   std::vector<uint16_t> dec;
   rc = decode_matrix(c, valid, invalid, dec, &plan.pattern_uses);
@@ -1092,6 +1149,30 @@ int run_plan_tail(const rse_codec* c, const ReconPlan& plan, size_t off, uint64_
 // Every data shard of a k = p = 16 / 32 / 64 (RSE_OPT_FFT 2: and 128) GF(2^8) codec rebuilt from its
 // parity shards: run_job codes the plan's rows on the additive-FFT kernels
 // (rse_fft.hip), so neither a pattern module nor the syndrome kernels apply.
+// RSE_OPT_FFT16: the plan's whole 4 KiB columns on the pruned-FFT kernel
+// (rse_fft16.hip), the bytes past them (and misaligned or short shards) on the
+// table kernels with the plan's rows.
+int run_fft16_plan(const rse_codec* c, ReconPlan& plan, uint64_t stripe_stride,
+                   size_t n_stripes, hipStream_t s) {
+  const size_t len = plan.len * c->esize();
+  uint64_t done = 0;
+  bool al = len >= 4096 && stripe_stride % 16u == 0 && n_stripes <= 0xffffffffu &&
+            rse::get_option(RSE_OPT_BITSLICE);
+  for (const uint8_t* q : plan.fft16_in) al = al && aligned16(q);
+  for (const uint8_t* q : plan.out) al = al && aligned16(q);
+  if (al)
+    RSE_HIP(rse::launch_fft16(*plan.fft16, plan.fft16_in.data(), (uint32_t)plan.out.size(),
+                              plan.fft16_pattern.mat.data(), plan.out.data(), nullptr, len,
+                              stripe_stride,
+                              (uint32_t)n_stripes, rse::kStore, nullptr, false, "rebuild", s, &done));
+  if (done == len) return RSE_OK;
+  rse::fft16_pattern_rows(*plan.fft16, plan.fft16_pattern, plan.rows.c);
+  const std::string kernel = done ? rse::last_kernel() : std::string();
+  const int rc = run_plan_tail(c, plan, done, stripe_stride, n_stripes, s);
+  if (done) rse::note_kernel("%s", kernel.c_str());
+  return rc;
+}
+
 bool fft_plan(const rse_codec* c, const ReconPlan& plan) {
   return plan.rows.n_in == plan.rows.n_out &&
          rse::fft_applies(c->kfield, (uint32_t)plan.rows.n_in, (uint32_t)plan.rows.n_out,
@@ -1102,8 +1183,9 @@ int reconstruct_impl(const rse_codec* c, void* const* shards, const size_t* lens
                      const uint8_t* present, size_t n, bool data_only, hipStream_t s) {
   if (!c) return RSE_ERR_INVALID_ARGUMENT;
   ReconPlan plan;
-  int rc = plan_reconstruct(c, shards, lens, present, n, data_only, plan);
+  int rc = plan_reconstruct(c, shards, lens, present, n, data_only, plan, true);
   if (rc || plan.nothing_to_do || plan.rows.n_out == 0) return rc;
+  if (plan.fft16) return run_fft16_plan(c, plan, 0, 1, s);
   if (fft_plan(c, plan)) return run_plan_tail(c, plan, 0, 0, 1, s);
   if (pattern_kernel(c, plan, plan.len * c->esize())) {
     ++g_pattern_launches;
@@ -1133,9 +1215,10 @@ int flat_reconstruct(const rse_codec* c, uint8_t* base, size_t shard_len, size_t
   std::vector<size_t> lens(c->total, shard_len);
   for (size_t i = 0; i < c->total; ++i) ptrs[i] = base + i * sb;
   ReconPlan plan;
-  int rc = plan_reconstruct(c, ptrs.data(), lens.data(), present, c->total, data_only, plan);
+  int rc = plan_reconstruct(c, ptrs.data(), lens.data(), present, c->total, data_only, plan, true);
   if (rc || plan.nothing_to_do || plan.rows.n_out == 0) return rc;
   const uint64_t stride = (uint64_t)c->total * sb;
+  if (plan.fft16) return run_fft16_plan(c, plan, stride, n_stripes, s);
   if (fft_plan(c, plan)) return run_plan_tail(c, plan, 0, stride, n_stripes, s);
   if (pattern_kernel(c, plan, sb, sb * n_stripes)) {
     ++g_pattern_launches;
@@ -1788,6 +1871,8 @@ int rse_codec_kernel_kind(const rse_codec* c, int wait) {
   if (rse::bitslice_compiled(c->kfield, (uint32_t)c->k, (uint32_t)c->p)) return RSE_KERNELS_COMPILED;
   const Rows rows = parity_rows(c);
   if (rse::fft_applies(c->kfield, (uint32_t)c->k, (uint32_t)c->p, rows.c.data()))
+    return RSE_KERNELS_FFT;
+  if (rse::fft16_applies(c->kfield, (uint32_t)c->k, (uint32_t)c->p, rows.c.data()))
     return RSE_KERNELS_FFT;
   if (wait) want_bitslice(c, rse::bitslice_chunk_bytes(), true);
   const bool wide = c->k > (size_t)kMaxIn || c->p > rse::kJitMaxOut ||
