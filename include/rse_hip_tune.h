@@ -129,5 +129,10 @@
                                          verifies and reconstructs on one compiled pruned additive-FFT
                                          kernel with run-time tables (rse_fft16.hip; same bytes):
                                          usable at once, no run-time module is built or requested */
+#define RSE_OPT_TICKET_GRID 55        /* compiled codecs' ticket kernels (RSE_OPT_KERNEL_VARIANT 10 /
+                                         11: 16 KiB chunks claimed from a device counter): workgroups
+                                         launched = this x the workgroups the device holds at once
+                                         (the kernel's occupancy x compute units); 1..16, default 1.
+                                         RSE_OPT_GRID_X > 0 still sets the count outright */
 
 #endif /* RSE_HIP_TUNE_H */

@@ -17,6 +17,7 @@
 // speed, never correctness.
 #include <atomic>
 #include "rse_bitslice_core.hpp"
+#include "rse_bitslice_ticket.hpp"
 
 namespace rse {
 namespace {
@@ -48,6 +49,14 @@ template <class C, int D>
 __global__ __launch_bounds__(kBsBlock, C::p > 4 ? 2 : 3) void bitslice_deep_kernel(
     const CodeArgs a, uint64_t chunks_per_stripe) {
   bitslice_body_deep<C, true, D>(a, chunks_per_stripe);
+}
+
+// Chunks claimed from a device counter (rse_bitslice_ticket.hpp): NL = 1 one
+// counter, NL = 8 one per label blockIdx.x % 8 with stealing.
+template <class C, int NL>
+__global__ __launch_bounds__(kBsBlock, C::p > 4 ? 2 : 3) void bitslice_ticket_kernel(
+    const CodeArgs a, uint64_t chunks_per_stripe, uint32_t* ticket) {
+  bitslice_body_ticket<C, NL>(a, chunks_per_stripe, ticket);
 }
 
 // ----------------------------------------------- LDS-DMA input ring variant
@@ -406,15 +415,20 @@ using BsDesc4Fn = void (*)(const BsReconArgs*, uint64_t, uint64_t, uint64_t);
 using BsRec4Fn = void (*)(const BsReconArgs, uint64_t, uint64_t);
 
 using BsFn = void (*)(const CodeArgs, uint64_t);
+using BsTicketFn = void (*)(const CodeArgs, uint64_t, uint32_t*);
+constexpr int kBsVariants = 12;  // RSE_OPT_KERNEL_VARIANT 0..11
 struct BsShape {
   int field;
   uint32_t k, p;
   const uint16_t* m;  // P x K parity rows compiled into the kernel
-  BsFn fn[10][2];     // [variant][nt]: 0 plain, 1 +sched barrier, 2 +cross-chunk
+  BsFn fn[kBsVariants][2];  // [variant][nt]: 0 plain, 1 +sched barrier, 2 +cross-chunk
                       // prefetch, 3/4 LDS-DMA input ring of 3/2 slots, 5/6 two/three
                       // inputs in flight in VGPRs, 7 = 1 in XCD-aware order, 8 = 1 with
                       // write-through (sc1) stores ([8][0] sc1, [8][1] sc1 nt), 9 = 1
-                      // without shared subexpressions (GF(2^16); = 1 for GF(2^8))
+                      // without shared subexpressions (GF(2^16); = 1 for GF(2^8)); 10 / 11
+                      // are tk[0] / tk[1] (another signature: nullptr here)
+  BsTicketFn tk[2];   // chunks claimed from a device counter: [0] variant 10, one
+                      // counter; [1] variant 11, one per label blockIdx.x % 8 (nt)
   BsFn w4;            // 4 KiB chunks, one per wave (variant 1's scheme, nt)
   BsFn sub[2];        // the same over 1 / 2 KiB shards, 4 / 2 stripes per chunk (SUB)
   BsFn chk;           // the default variant for the check modes (verify): the
@@ -495,7 +509,10 @@ constexpr BsDescFn rec_desc_deep_fn() {
     {nullptr, bitslice_kernel<C, true, true, false, true>},                        \
     {bitslice_kernel<C, false, true, false, false, true>,                          \
      bitslice_kernel<C, true, true, false, false, true>},                          \
-    {nullptr, bitslice_kernel<CP, true, true, false>}},                            \
+    {nullptr, bitslice_kernel<CP, true, true, false>},                             \
+    {nullptr, nullptr},                                                            \
+    {nullptr, nullptr}},                                                           \
+   {bitslice_ticket_kernel<C, 1>, bitslice_ticket_kernel<C, 8>},                   \
    bitslice_kernel<C, true, true, false, false, false, true>,                      \
    {bitslice_kernel<C, true, true, false, false, false, true, false, 1024u>,       \
     bitslice_kernel<C, true, true, false, false, false, true, false, 2048u>},      \
@@ -550,6 +567,38 @@ uint32_t device_cus() {
   return c;
 }
 
+// Workgroups of ticket kernel `f` the current device holds at once: the
+// runtime's occupancy of that kernel times the compute units (cached per
+// device and kernel, `slot` < 8 its index).
+uint64_t ticket_resident(BsTicketFn f, int slot) {
+  static std::atomic<uint32_t> held[64][8];  // zero-initialised (static storage)
+  int dev = 0;
+  const bool cache = hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64 && slot >= 0 && slot < 8;
+  uint32_t r = cache ? held[dev][slot].load(std::memory_order_relaxed) : 0u;
+  if (!r) {
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, f, kBsBlock, 0) != hipSuccess ||
+        per_cu < 1)
+      per_cu = 1;
+    r = (uint32_t)per_cu * device_cus();
+    if (cache) held[dev][slot].store(r, std::memory_order_relaxed);
+  }
+  return r;
+}
+
+// The ticket variant that store-mode GF(2^8) launches of more than
+// kBsTicketMinRounds rounds of resident workgroups take by default (10 or 11),
+// 0: none.  DESIGN.md §5 (profiles/ticket/): variant 11's slowest run beats
+// variant 5's fastest in the in-process A/B and in the bench A/B; 10+2 x 1 MiB
+// x 2048 stripes and 20+8 x 4 MiB x 256 gain too (ab_10_2.log, ab_20_8.log).
+// 85 rounds: the smallest launch measured to gain (10+4 x 16 MiB x 64 stripes,
+// 85.3 rounds, ab_64_stripes.log).  Launches of 2 to 4 rounds lose a third in
+// back-to-back calls (ab_3_stripes.log, ab_2_stripes.log,
+// ab_1_stripe_24mib.log); 8 to 64 rounds lose 18 % to nothing
+// (sweep_*_stripes.log): the crossover lies between 64 and 85.
+constexpr int kBsTicketDefault = 11;
+constexpr uint64_t kBsTicketMinRounds = 85;
+
 hipError_t launch_bitslice(int field, const CodeArgs& a, bool nt, int64_t grid,
                            hipStream_t stream, bool* handled, uint64_t* done) {
   *handled = false;
@@ -566,6 +615,8 @@ hipError_t launch_bitslice(int field, const CodeArgs& a, bool nt, int64_t grid,
   bool compiled = false;
   int vopt_used = -1;
   bool chk = false;  // f16 is the compiled check kernel (it reads a.done)
+  const BsShape* shape = nullptr;  // the compiled shape
+  int tk_slot = -1;                // RSE_OPT_KERNEL_VARIANT 10 / 11: BsShape::tk[0 / 1]
   for (const BsShape& sh : kBsShapes) {
     if (a.accumulate) break;
     if (sh.field != field || sh.k != a.n_in || sh.p != a.n_out) continue;
@@ -575,8 +626,13 @@ hipError_t launch_bitslice(int field, const CodeArgs& a, bool nt, int64_t grid,
     if (!same) break;
     // RSE_OPT_KERNEL_VARIANT picks a bit-sliced variant too (-1: default)
     const int64_t vopt = get_option(4);
-    int v = (vopt >= 0 && vopt < 10) ? (int)vopt
-                                     : (field == 16 ? kBsDefaultVariant16 : kBsDefaultVariant8);
+    const int vdef = field == 16 ? kBsDefaultVariant16 : kBsDefaultVariant8;
+    int v = (vopt >= 0 && vopt < kBsVariants) ? (int)vopt : vdef;
+    shape = &sh;
+    if (v >= 10) {  // the ticket kernels; f16 stays the default's for launches they do not take
+      tk_slot = v - 10;
+      v = vdef;
+    }
     f16 = sh.fn[v][nt ? 1 : 0];
     if (!f16) f16 = sh.fn[v][1];
     if (a.mode != kStore && vopt < 0 && nt) {
@@ -651,6 +707,27 @@ hipError_t launch_bitslice(int field, const CodeArgs& a, bool nt, int64_t grid,
   }
   // whole 16 KiB chunks, then whole 4 KiB chunks of the rest (one per wave)
   const uint64_t cps16 = a.n_vec / kV16, cps4 = (a.n_vec - cps16 * kV16) / kV4;
+  // The 16 KiB chunks claimed from a device counter (rse_bitslice_ticket.hpp):
+  // RSE_OPT_KERNEL_VARIANT 10 / 11 at any size; by default (kBsTicketDefault)
+  // GF(2^8) store-mode launches of more than kBsTicketMinRounds rounds of
+  // resident workgroups -- anything smaller keeps today's path (the one-stripe
+  // call's 40.9 us).  The counters are 32-bit.
+  BsTicketFn ftk = nullptr;
+  if (compiled && cps16 && cps16 * a.n_stripes < 0x40000000u) {
+    if (tk_slot < 0 && kBsTicketDefault >= 10 && get_option(4) < 0 && field == 8 && nt &&
+        a.mode == kStore) {
+      // rounds of the workgroups the ticket kernel itself holds (its occupancy), as its grid
+      const int d = kBsTicketDefault - 10;
+      if (cps16 * a.n_stripes >
+          kBsTicketMinRounds * ticket_resident(shape->tk[d], (int)(shape - kBsShapes) * 2 + d))
+        tk_slot = d;
+    }
+    if (tk_slot >= 0) {
+      ftk = shape->tk[tk_slot];
+      vopt_used = 10 + tk_slot;
+      nt = true;
+    }
+  }
   if (compiled)
     note_kernel("bitslice gf%d %u+%u v%d nt%d%s", field, a.n_in, a.n_out,
                 (int)(vopt_used), nt ? 1 : 0, cps16 ? "" : " w4");
@@ -668,7 +745,28 @@ hipError_t launch_bitslice(int field, const CodeArgs& a, bool nt, int64_t grid,
     const bool arm = a.done && chk && a.mode == kCheck && a.n_vec == cps16 * kV16 &&
                      a.len == a.n_vec * 16u;
     hipError_t e;
-    if (a.done && !arm) {
+    if (ftk) {
+      // Grid: what the device holds at once (the kernel's own occupancy) times
+      // RSE_OPT_TICKET_GRID -- every workgroup resident from the start, no
+      // partial last round (profiles/ticket/grid_sweep.log, timeline.log).
+      const uint64_t total = cps16 * a.n_stripes;
+      uint64_t gx = ticket_resident(ftk, (int)(shape - kBsShapes) * 2 + tk_slot) *
+                    (uint64_t)get_option(55);
+      if (gx > total) gx = total;
+      if (grid > 0) gx = (uint64_t)grid < 0x20000000u ? (uint64_t)grid : 0x20000000u;
+      // The counter words live for this launch only: allocated, zeroed and
+      // released in stream order, so launches on other streams never share them.
+      uint32_t* words = nullptr;
+      e = hipMallocAsync(reinterpret_cast<void**>(&words), kTkWords * sizeof(uint32_t), stream);
+      if (e != hipSuccess) return e;
+      e = hipMemsetAsync(words, 0, kTkWords * sizeof(uint32_t), stream);
+      if (e == hipSuccess) {
+        hipLaunchKernelGGL(ftk, dim3((uint32_t)gx), dim3(kBsBlock), 0, stream, a, cps16, words);
+        e = hipGetLastError();
+      }
+      const hipError_t f = hipFreeAsync(words, stream);
+      if (e == hipSuccess) e = f;
+    } else if (a.done && !arm) {
       CodeArgs c = a;
       c.done = c.done_count = nullptr;
       e = launch(f16, j16, c, cps16, cps16 * a.n_stripes);

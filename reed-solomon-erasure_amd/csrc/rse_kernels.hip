@@ -810,6 +810,7 @@ struct Options {
   int64_t fft = 1;  // GF(2^8) k = p = 16 / 32 / 64 (2: and 128) codecs on the additive-FFT kernels (rse_fft.hip)
   int64_t host_queues = 1;  // host pipeline: 1 the D2H stream at high priority, 0 plain (A/B)
   int64_t host_zc_out = 1;  // host pipeline: outputs stored in place in mapped pinned memory
+  int64_t ticket_grid = 1;  // ticket kernels (rse_bitslice_ticket.hpp): workgroups = this x resident
   int64_t fft16 = 0;  // GF(2^16) codecs past 256 shards with 2^m - k <= 32 on the pruned-FFT kernel (rse_fft16.hip)
 };
 thread_local int64_t g_bs_launches = 0;  // bit-sliced launches on this thread (RSE_OPT 6)
@@ -1363,6 +1364,7 @@ int set_option(int key, int64_t value) {
     case 52: g_opt.host_queues = value ? 1 : 0; return 0;
     case 53: g_opt.host_zc_out = value ? 1 : 0; return 0;
     case 54: g_opt.fft16 = value ? 1 : 0; return 0;
+    case 55: g_opt.ticket_grid = value < 1 ? 1 : value > 16 ? 16 : value; return 0;
 #ifdef RSE_TUNE_SPLITS
     case 47: g_opt.tune_nosync = value ? 1 : 0; return 0;  // rse_jit.cpp make_source
 #endif
@@ -1428,6 +1430,7 @@ int64_t get_option(int key) {
     case 52: return g_opt.host_queues;
     case 53: return g_opt.host_zc_out;
     case 54: return g_opt.fft16;
+    case 55: return g_opt.ticket_grid;
 #ifdef RSE_TUNE_SPLITS
     case 47: return g_opt.tune_nosync;
 #endif

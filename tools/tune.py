@@ -43,7 +43,11 @@ def main():
                     help="batch: rse_reconstruct_batch, every stripe its own random pattern "
                          "of len(--erase) erased shards")
     ap.add_argument("--variants", type=int, default=1)
-    ap.add_argument("--variant-list", default="", help="comma list of variants (overrides --variants)")
+    ap.add_argument("--variant-list", default="",
+                    help="comma list of variants (overrides --variants); 10 / 11 are the ticket "
+                         "kernels (chunks claimed from one device counter / one per XCD label), "
+                         "whose automatic grid (grid_x 0) is RSE_OPT_TICKET_GRID (--set 55=N) x "
+                         "the resident workgroups")
     ap.add_argument("--bitslice", default="1", help="comma list of RSE_OPT_BITSLICE values")
     ap.add_argument("--shapes", default="", help="gx:gy,gx:gy,... (default: built-in list)")
     ap.add_argument("--erase", default="0,1", help="reconstruct: erased shard indices")
