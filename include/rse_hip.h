@@ -157,6 +157,46 @@ int rse_encode_flat(const rse_codec *codec, void *stripes, size_t shard_len,
  * call; this is the batched form of the same check for scrubbing.) */
 int rse_verify_flat(const rse_codec *codec, const void *stripes, size_t shard_len,
                     size_t n_stripes, uint8_t *ok, rse_stream_t stream);
+/* Error LOCATION over the same layout: which shards of each stripe are wrong,
+ * so that a scrub can repair what rse_verify_flat can only report.  (No
+ * reference counterpart: the crate handles erasures only.)  The code is a
+ * Reed-Solomon code of minimum distance p+1 (core.rs:430-436: every byte
+ * column of a stripe is a polynomial of degree < k evaluated at 0..k+p-1), so
+ * up to t = p/2 wrong shards per byte column are located exactly, by syndrome
+ * decoding, in one pass that reads every shard once and writes only flags.
+ * Per byte column: it is CLEAN if it is a codeword; DECODABLE if exactly one
+ * codeword lies within Hamming distance t of it (its bad shards are where it
+ * differs from that codeword); otherwise UNDECODABLE.  Per stripe s:
+ *   every column clean                          status[s] = RSE_LOCATE_CLEAN,
+ *                                               present row all 1;
+ *   any column undecodable, or the union of bad shards over all columns has
+ *   more than p members                         RSE_LOCATE_UNCORRECTABLE,
+ *                                               present row all 1 (a
+ *                                               reconstruct leaves it alone);
+ *   otherwise                                   RSE_LOCATE_LOCATED, present 0
+ *                                               exactly at the union, 1 elsewhere.
+ * Different columns may have different bad shards: a union of more than t (up
+ * to p) shards is still LOCATED as long as no single column needs more than t.
+ * INHERENT LIMIT: a column with MORE than t wrong shards can lie within t of a
+ * different codeword; it is then "decodable" and innocent shards are named.
+ * Confirm a repair with rse_verify_flat.
+ * present (n_stripes x (k+p) bytes) and status (n_stripes bytes) are DEVICE
+ * memory of the stripes' device, written by kernels; stripes is only read.
+ * Asynchronous on `stream`, no host synchronisation (the first call of a codec
+ * on a device copies its plan there, once).  present can be handed unchanged
+ * to rse_reconstruct_batch, which reads device flags in place.
+ * Validation, before any device call, in this order: NULL codec / stripes /
+ * present / status -> RSE_ERR_INVALID_ARGUMENT; a codec out of scope ->
+ * RSE_ERR_INVALID_ARGUMENT (in scope: GF(2^8), 1 <= p <= 16, k + p <= 255;
+ * GF(2^16) codecs, p > 16 and k + p = 256 are not supported, nor host memory);
+ * shard_len == 0 -> RSE_EMPTY_SHARD; n_stripes == 0 -> RSE_OK, nothing touched.
+ * Any shard_len >= 1 works, at whatever alignment the layout gives the shards. */
+#define RSE_LOCATE_CLEAN 0         /* every column is a codeword */
+#define RSE_LOCATE_LOCATED 1       /* bad shards named; at most p of them */
+#define RSE_LOCATE_UNCORRECTABLE 2 /* some column is not within t = p/2 errors of a
+                                      codeword, or more than p shards are implicated */
+int rse_locate_flat(const rse_codec *codec, const void *stripes, size_t shard_len,
+                    size_t n_stripes, uint8_t *present, uint8_t *status, rse_stream_t stream);
 /* Same layout; every stripe has the same erasure pattern `present[k+p]`
  * (wasm reconstruct(): reconstruct_data semantics). */
 int rse_reconstruct_data_flat(const rse_codec *codec, void *stripes, size_t shard_len,

@@ -31,6 +31,8 @@
 #include "rse_dispatch.hpp"
 #include "rse_fft.hpp"
 #include "rse_fft16.hpp"
+#include "rse_locate.hpp"
+#include "rse_locate_plan.hpp"
 #include "rse_wideblk.hpp"
 #include "rse_field.hpp"
 #include "rse_kernels.hpp"
@@ -98,8 +100,13 @@ struct rse_codec {
   // a call copies neither.
   static constexpr int kDevs = 64;
   mutable std::atomic<uint8_t*> plan_dev[kDevs] = {};
+  // Per device: rse_locate_flat's plan (rse_locate_plan.hpp locate_consts),
+  // made on the first locate there and kept likewise (locate_plan_consts).
+  mutable std::atomic<uint8_t*> locate_dev[kDevs] = {};
   ~rse_codec() {
     for (auto& a : plan_dev)
+      if (uint8_t* q = a.load()) (void)hipFree(q);
+    for (auto& a : locate_dev)
       if (uint8_t* q = a.load()) (void)hipFree(q);
   }
 
@@ -758,6 +765,35 @@ hipError_t plan_consts(const rse_codec* c, int dev, const uint8_t** out) {
   }
   uint8_t* expect = nullptr;
   if (!c->plan_dev[dev].compare_exchange_strong(expect, q, std::memory_order_acq_rel)) {
+    (void)hipFree(q);
+    q = expect;
+  }
+  *out = q;
+  return hipSuccess;
+}
+
+// The codec's locate plan on device `dev` (rse_codec::locate_dev), as
+// plan_consts: made once per device with a synchronous copy, which the first
+// rse_locate_flat there pays; every later call is asynchronous.
+hipError_t locate_plan_consts(const rse_codec* c, int dev, const uint8_t** out) {
+  if (dev < 0 || dev >= rse_codec::kDevs) return hipErrorInvalidDevice;
+  if (uint8_t* q = c->locate_dev[dev].load(std::memory_order_acquire)) {
+    *out = q;
+    return hipSuccess;
+  }
+  const Rows r = parity_rows(c);
+  const rse::LocatePlan pl = rse::make_locate_plan(c->k, c->p, r.c.data());
+  std::vector<uint8_t> h(rse::locate_consts_bytes(pl), 0);
+  rse::locate_consts(pl, h.data());
+  uint8_t* q = nullptr;
+  hipError_t e = hipMalloc(reinterpret_cast<void**>(&q), h.size());
+  if (e == hipSuccess) e = hipMemcpy(q, h.data(), h.size(), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    if (q) (void)hipFree(q);
+    return e;
+  }
+  uint8_t* expect = nullptr;
+  if (!c->locate_dev[dev].compare_exchange_strong(expect, q, std::memory_order_acq_rel)) {
     (void)hipFree(q);
     q = expect;
   }
@@ -2153,6 +2189,41 @@ int rse_verify_flat(const rse_codec* c, const void* stripes, size_t shard_len, s
   if (rc == RSE_OK)
     for (size_t s = 0; s < n_stripes; ++s) ok[s] = (uint8_t)res[s];
   return rc;
+}
+
+// Which shards of every stripe are wrong (rse_locate.hip): the locating pass
+// into per-stripe accumulators in a stream-ordered workspace, then the pass
+// that writes present / status.  Validation first; no host synchronisation
+// (the codec's plan is copied to the device once, on the first call there).
+int rse_locate_flat(const rse_codec* c, const void* stripes, size_t shard_len, size_t n_stripes,
+                    uint8_t* present, uint8_t* status, rse_stream_t stream) {
+  if (!c || !stripes || !present || !status) return RSE_ERR_INVALID_ARGUMENT;
+  if (!rse::locate_in_scope(c->field, c->k, c->p)) return RSE_ERR_INVALID_ARGUMENT;
+  if (shard_len == 0) return RSE_EMPTY_SHARD;
+  if (n_stripes == 0) return RSE_OK;
+  RSE_ON_STREAM(stream);
+  hipStream_t st = (hipStream_t)stream;
+  int dev = 0;
+  RSE_HIP(hipGetDevice(&dev));
+  const uint8_t* consts = nullptr;
+  RSE_HIP(locate_plan_consts(c, dev, &consts));
+  uint32_t* acc = nullptr;
+  RSE_HIP(hipMallocAsync(reinterpret_cast<void**>(&acc),
+                         n_stripes * rse::kLocAccWords * sizeof(uint32_t), st));
+  rse::LocateArgs a{};
+  a.base = static_cast<const uint8_t*>(stripes);
+  a.shard_bytes = shard_len;
+  a.n_stripes = n_stripes;
+  a.k = (uint32_t)c->k;
+  a.p = (uint32_t)c->p;
+  a.consts = consts;
+  a.acc = acc;
+  const hipError_t e = rse::launch_locate(a, present, status, st);
+  const hipError_t f = hipFreeAsync(acc, st);
+  if (e != hipSuccess) return dev_fail(e);
+  if (f != hipSuccess) return dev_fail(f);
+  rse::note_kernel("locate gf8 %zu+%zu", c->k, c->p);
+  return RSE_OK;
 }
 
 int rse_reconstruct_data_flat(const rse_codec* c, void* stripes, size_t shard_len,

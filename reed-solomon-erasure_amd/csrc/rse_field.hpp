@@ -31,6 +31,10 @@ class Gf8 {
     if (a == 0) return 0;
     return t().exp[(size_t)t().log[a] * (n % 255) % 255];
   }
+  // The tables themselves (log[256], then exp[512] doubled so that
+  // exp[log a + log b] needs no reduction): what device decoders copy to LDS.
+  static const uint8_t* log_table() { return t().log; }
+  static const uint8_t* exp_table() { return t().exp; }
 
  private:
   struct Tables {

@@ -18,6 +18,11 @@ from .errors import DeviceError, Error, RSError, SBSError, SBSErrorKind
 
 _lib = load()
 
+# rse_locate_flat's per-stripe status (include/rse_hip.h RSE_LOCATE_*)
+LOCATE_CLEAN = 0
+LOCATE_LOCATED = 1
+LOCATE_UNCORRECTABLE = 2
+
 ShardList = Sequence[torch.Tensor]
 
 
@@ -344,6 +349,27 @@ class ReedSolomon:
                                     ok.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
                                     _stream(stripes)))
         return ok[:n_stripes].astype(bool)
+
+    def locate_flat(self, stripes: torch.Tensor, shard_len: int,
+                    n_stripes: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Which shards of every stripe of the flat layout are wrong
+        (rse_locate_flat): returns ``(present, status)``, uint8 device tensors
+        of shapes ``(n_stripes, k+p)`` and ``(n_stripes,)``.  ``status`` is
+        LOCATE_CLEAN, LOCATE_LOCATED (``present`` is 0 exactly at the bad
+        shards) or LOCATE_UNCORRECTABLE (``present`` all 1).  Queued on the
+        current stream, no synchronisation; ``present`` goes unchanged into
+        reconstruct_batch().  GF(2^8) codecs with p <= 16 and k + p <= 255;
+        up to p // 2 wrong shards per byte column are located exactly --
+        confirm a repair with verify_flat()."""
+        T = self.total_shard_count()
+        _check_flat(stripes, shard_len, n_stripes, T, self.field)
+        base = _dev(stripes)
+        # at least one row: an empty tensor has no address to pass
+        present = torch.empty((max(1, n_stripes), T), dtype=torch.uint8, device=stripes.device)
+        status = torch.empty((max(1, n_stripes),), dtype=torch.uint8, device=stripes.device)
+        _raise(_lib.rse_locate_flat(self._h, base, shard_len, n_stripes, present.data_ptr(),
+                                    status.data_ptr(), _stream(stripes)))
+        return present[:n_stripes], status[:n_stripes]
 
     def reconstruct_data_flat(self, stripes: torch.Tensor, shard_len: int, n_stripes: int,
                               present: Sequence[bool]) -> None:
