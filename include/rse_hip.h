@@ -197,6 +197,56 @@ int rse_verify_flat(const rse_codec *codec, const void *stripes, size_t shard_le
                                       codeword, or more than p shards are implicated */
 int rse_locate_flat(const rse_codec *codec, const void *stripes, size_t shard_len,
                     size_t n_stripes, uint8_t *present, uint8_t *status, rse_stream_t stream);
+/* Error CORRECTION over the same layout, in place: the wrong bytes of every
+ * stripe are repaired where they lie, in the one pass that finds them, and
+ * known-missing shards (erasures) may be combined with unknown corruption.
+ * (No reference counterpart.)  Same scope as rse_locate_flat.
+ * present (nullable; n_stripes x (k+p) flags in DEVICE memory, read in place):
+ * non-zero = present, 0 = erased, the convention of rse_reconstruct_batch and
+ * of rse_locate_flat's output, so a locate result can be fed straight in.
+ * NULL: nothing is erased.  An erased shard's buffer must exist; its contents
+ * are arbitrary.  Let f be the number of erased shards of a stripe.
+ * PER BYTE COLUMN (every byte column is its own codeword): the column is
+ * DECODABLE when some codeword differs from it in nu positions outside the
+ * erased set, and anywhere inside it, with 2 nu + f <= p; that codeword is
+ * unique (minimum distance p+1).  A decodable column is overwritten with that
+ * codeword -- only the bytes that differ are stored; an undecodable column is
+ * left byte for byte as it was.  COLUMNS ARE INDEPENDENT: a stripe with an
+ * undecodable column still gets its other columns repaired, and so may be
+ * partly repaired when its status is RSE_CORRECT_UNCORRECTABLE.  A caller that
+ * wants all-or-nothing per stripe runs rse_locate_flat first.  This also means
+ * that a stripe whose columns implicate more than p shards between them, which
+ * rse_locate_flat reports UNCORRECTABLE, is repaired here as long as no single
+ * column needs more than its own 2 nu + f <= p.
+ * If f > p the stripe is not touched at all (and not read).
+ * INHERENT LIMIT: a column with more than (p-f)/2 errors may lie within reach
+ * of another codeword; it is then decoded to that codeword.  Confirm with
+ * rse_verify_flat.
+ * Outputs, DEVICE memory of the stripes' device, written by kernels:
+ *   status[s]      RSE_CORRECT_CLEAN / _CORRECTED / _UNCORRECTABLE (n_stripes);
+ *   changed[s][r]  (nullable, n_stripes x (k+p)) 1 iff at least one byte of
+ *                  shard r of stripe s was stored with a new value, else 0;
+ *   counts[s]      (nullable, n_stripes x 2) {bytes stored, columns left
+ *                  undecodable}; they saturate at 2^32-1 and never wrap; a
+ *                  stripe skipped for f > p reports {0, 0}.
+ * Asynchronous on `stream`, no host synchronisation (the codec's plan is
+ * copied to a device once, the copy rse_locate_flat uses).
+ * Validation, before any device call, in rse_locate_flat's order and with its
+ * codes: NULL codec / stripes / status -> RSE_ERR_INVALID_ARGUMENT (present,
+ * changed and counts may be NULL); a codec out of scope ->
+ * RSE_ERR_INVALID_ARGUMENT; shard_len == 0 -> RSE_EMPTY_SHARD; n_stripes == 0
+ * -> RSE_OK, nothing touched.  Any shard_len >= 1 works, at whatever alignment
+ * the layout gives the shards. */
+#define RSE_CORRECT_CLEAN 0          /* every column was a codeword; nothing written */
+#define RSE_CORRECT_CORRECTED 1      /* every column is a codeword now */
+#define RSE_CORRECT_UNCORRECTABLE 2  /* some column left as it was, or more than p shards erased
+                                        (then nothing of the stripe is written) */
+int rse_correct_flat(const rse_codec *codec, void *stripes, size_t shard_len, size_t n_stripes,
+                     const uint8_t *present, /* nullable */
+                     uint8_t *status,        /* n_stripes */
+                     uint8_t *changed,       /* nullable, n_stripes x (k+p) */
+                     uint32_t *counts,       /* nullable, n_stripes x 2 */
+                     rse_stream_t stream);
 /* Same layout; every stripe has the same erasure pattern `present[k+p]`
  * (wasm reconstruct(): reconstruct_data semantics). */
 int rse_reconstruct_data_flat(const rse_codec *codec, void *stripes, size_t shard_len,

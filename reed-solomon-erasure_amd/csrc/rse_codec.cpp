@@ -31,6 +31,8 @@
 #include "rse_dispatch.hpp"
 #include "rse_fft.hpp"
 #include "rse_fft16.hpp"
+#include "rse_correct.hpp"
+#include "rse_correct_plan.hpp"
 #include "rse_locate.hpp"
 #include "rse_locate_plan.hpp"
 #include "rse_wideblk.hpp"
@@ -783,8 +785,9 @@ hipError_t locate_plan_consts(const rse_codec* c, int dev, const uint8_t** out) 
   }
   const Rows r = parity_rows(c);
   const rse::LocatePlan pl = rse::make_locate_plan(c->k, c->p, r.c.data());
-  std::vector<uint8_t> h(rse::locate_consts_bytes(pl), 0);
-  rse::locate_consts(pl, h.data());
+  // rse_locate_flat's layout, then what rse_correct_flat adds: one copy serves both
+  std::vector<uint8_t> h(rse::kCorConstsBytes, 0);
+  rse::correct_consts(pl, h.data());
   uint8_t* q = nullptr;
   hipError_t e = hipMalloc(reinterpret_cast<void**>(&q), h.size());
   if (e == hipSuccess) e = hipMemcpy(q, h.data(), h.size(), hipMemcpyHostToDevice);
@@ -2223,6 +2226,44 @@ int rse_locate_flat(const rse_codec* c, const void* stripes, size_t shard_len, s
   if (e != hipSuccess) return dev_fail(e);
   if (f != hipSuccess) return dev_fail(f);
   rse::note_kernel("locate gf8 %zu+%zu", c->k, c->p);
+  return RSE_OK;
+}
+
+// Repairs the wrong bytes of every stripe where they lie (rse_correct.hip):
+// the repairing pass, which also fills per-stripe accumulators in a
+// stream-ordered workspace, then the pass that writes status / changed /
+// counts.  Validation first, in rse_locate_flat's order; no host
+// synchronisation (the plan is the one rse_locate_flat copies, once per device).
+int rse_correct_flat(const rse_codec* c, void* stripes, size_t shard_len, size_t n_stripes,
+                     const uint8_t* present, uint8_t* status, uint8_t* changed, uint32_t* counts,
+                     rse_stream_t stream) {
+  if (!c || !stripes || !status) return RSE_ERR_INVALID_ARGUMENT;
+  if (!rse::locate_in_scope(c->field, c->k, c->p)) return RSE_ERR_INVALID_ARGUMENT;
+  if (shard_len == 0) return RSE_EMPTY_SHARD;
+  if (n_stripes == 0) return RSE_OK;
+  RSE_ON_STREAM(stream);
+  hipStream_t st = (hipStream_t)stream;
+  int dev = 0;
+  RSE_HIP(hipGetDevice(&dev));
+  const uint8_t* consts = nullptr;
+  RSE_HIP(locate_plan_consts(c, dev, &consts));
+  uint32_t* acc = nullptr;
+  RSE_HIP(hipMallocAsync(reinterpret_cast<void**>(&acc),
+                         n_stripes * rse::kLocAccWords * sizeof(uint32_t), st));
+  rse::CorrectArgs a{};
+  a.loc.base = static_cast<const uint8_t*>(stripes);
+  a.loc.shard_bytes = shard_len;
+  a.loc.n_stripes = n_stripes;
+  a.loc.k = (uint32_t)c->k;
+  a.loc.p = (uint32_t)c->p;
+  a.loc.consts = consts;
+  a.loc.acc = acc;
+  a.present = present;
+  const hipError_t e = rse::launch_correct(a, status, changed, counts, st);
+  const hipError_t f = hipFreeAsync(acc, st);
+  if (e != hipSuccess) return dev_fail(e);
+  if (f != hipSuccess) return dev_fail(f);
+  rse::note_kernel("correct gf8 %zu+%zu", c->k, c->p);
   return RSE_OK;
 }
 

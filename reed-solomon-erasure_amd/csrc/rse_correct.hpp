@@ -1,0 +1,28 @@
+// rse_correct.hpp -- launch interface of the in-place repair kernels
+// (rse_correct.hip) behind rse_correct_flat.
+#pragma once
+
+#include "rse_locate.hpp"
+
+namespace rse {
+
+// A stripe's accumulator, kLocAccWords words as rse_locate_flat's: bit r of
+// the 8 mask words = a byte of shard r was stored; then two 64-bit counters,
+// bytes stored and columns left undecodable; then the word that says the
+// stripe was skipped (more than p shards erased).
+constexpr uint32_t kCorAccStored = 8;   // words 8, 9
+constexpr uint32_t kCorAccBad = 10;     // words 10, 11
+constexpr uint32_t kCorAccSkipped = 12;
+
+struct CorrectArgs {
+  LocateArgs loc;          // the stripes (written in place), the plan, the accumulators
+  const uint8_t* present;  // n_stripes x (k + p), 0 = erased; null: nothing is erased
+};
+
+// The repairing pass over every stripe, then the pass that turns the
+// accumulators into status (n_stripes), changed (n_stripes x (k + p), nullable)
+// and counts (n_stripes x 2, nullable).
+hipError_t launch_correct(const CorrectArgs& a, uint8_t* status, uint8_t* changed,
+                          uint32_t* counts, hipStream_t stream);
+
+}  // namespace rse

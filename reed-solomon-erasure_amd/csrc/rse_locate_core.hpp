@@ -1,0 +1,177 @@
+// rse_locate_core.hpp -- the fast path the kernels of rse_locate_flat
+// (rse_locate.hip) and rse_correct_flat (rse_correct.hip) share: one unit of a
+// workgroup's sweep forms d = P data ^ parity per byte column with the
+// arithmetic of the table check (rse_kernels.hip gf8_span in kCheck mode) and
+// hands the lanes with a nonzero d to the caller's slow path.  Device code
+// only; included by those two translation units.
+#pragma once
+
+#include "rse_device.hpp"
+#include "rse_locate.hpp"
+#include "rse_locate_plan.hpp"
+
+namespace rse {
+namespace locate_core {
+
+constexpr int kLocBlock = 256;
+constexpr int kLocKC = 4;  // inputs loaded before any arithmetic (as gf8_span's KC)
+
+// (input, output) tables a workgroup holds: 2048 x 20 B = 40 KiB, four
+// workgroups per CU.  NO = 16 past k = 128 rebuilds them per chunk of inputs.
+template <int NO>
+constexpr uint32_t loc_tabs() {
+  return NO == 4 ? 1024u : 2048u;
+}
+
+template <int NW>
+__device__ __forceinline__ void loc_load(const uint8_t* p, bool valid, uint32_t (&x)[NW]) {
+  if constexpr (NW == 4) {
+    uint4 v = make_uint4(0u, 0u, 0u, 0u);
+    if (valid) v = ld16<true>(p);
+    x[0] = v.x;
+    x[1] = v.y;
+    x[2] = v.z;
+    x[3] = v.w;
+  } else {
+    x[0] = valid ? (uint32_t)*(gptr<const uint8_t>)(p) : 0u;
+  }
+}
+
+template <int NO>
+__device__ __forceinline__ void loc_build_tabs(uint4* tq, uint32_t* tt2, const uint8_t* rows,
+                                               uint32_t k, uint32_t p, uint32_t c0, uint32_t kc) {
+  for (uint32_t t = threadIdx.x; t < p * kc; t += kLocBlock) {
+    const uint32_t r = t / kc, i = t % kc;
+    write_tab(tq, tt2, t, make_gf8_tab(rows[r * k + c0 + i]));
+  }
+}
+
+// d of the lane's byte column c, packed, out of the accumulators: unrolled
+// selects on values (rse_locate_plan.hpp pk_get), so that inside a rolled loop
+// over the columns the accumulators stay in VGPRs.
+template <int NO, int NW>
+__device__ __forceinline__ void loc_column_d(const uint32_t (&acc)[NO][NW], uint32_t c,
+                                             uint32_t (&d)[4]) {
+  d[0] = d[1] = d[2] = d[3] = 0u;
+#pragma unroll
+  for (int r = 0; r < NO; ++r) {
+    uint32_t v = acc[r][0];
+#pragma unroll
+    for (int w = 1; w < NW; ++w) {
+      const uint32_t aw = acc[r][w];  // read, then select
+      v = (c >> 2) == (uint32_t)w ? aw : v;
+    }
+    d[r >> 2] |= ((v >> ((c & 3u) * 8u)) & 0xFFu) << ((r & 3) * 8);
+  }
+}
+
+// One unit of a workgroup's sweep: lane t takes NW words of every shard at
+// byte offset `off` of the stripe at sbase (NW = 4: a 16-byte vector; NW = 1:
+// one byte, for the ragged tail and unaligned stripes).  Called by every
+// thread of the workgroup (MULTI rebuilds the tables between barriers).  A
+// wave whose d is zero in every lane is done; in any other, the lanes with a
+// nonzero d call slow(acc, sbase, off) -- the rare path, inlined so that the
+// accumulators are never passed through memory.
+template <int NO, int NW, bool MULTI, class Slow>
+__device__ __forceinline__ void loc_unit(const LocateArgs& a, uint4* tq, uint32_t* tt2,
+                                         const uint8_t* sbase, uint64_t off, bool valid,
+                                         const Slow& slow) {
+  constexpr uint32_t KCH = loc_tabs<NO>() / NO;
+  const uint32_t k = a.k, p = a.p;
+  uint32_t acc[NO][NW];
+#pragma unroll
+  for (int r = 0; r < NO; ++r)
+#pragma unroll
+    for (int w = 0; w < NW; ++w) acc[r][w] = 0u;
+  for (uint32_t c0 = 0; c0 < k; c0 += KCH) {
+    const uint32_t kc = k - c0 < KCH ? k - c0 : KCH;
+    if (MULTI) {
+      __syncthreads();
+      loc_build_tabs<NO>(tq, tt2, a.consts + kLocRowsOff, k, p, c0, kc);
+      __syncthreads();
+    }
+    const uint32_t lb = opaque_zero();
+    const uint8_t* in = sbase + (uint64_t)c0 * a.shard_bytes + off;
+    for (uint32_t i0 = 0; i0 < kc; i0 += kLocKC) {
+      uint32_t x[kLocKC][NW];
+#pragma unroll
+      for (int j = 0; j < kLocKC; ++j)
+        if (i0 + j < kc) loc_load<NW>(in + (uint64_t)(i0 + j) * a.shard_bytes, valid, x[j]);
+#pragma unroll
+      for (int j = 0; j < kLocKC; ++j) {
+        if (!(i0 + j < kc)) continue;
+        Sel sel[NW];
+#pragma unroll
+        for (int w = 0; w < NW; ++w) sel[w] = make_sel(x[j][w]);
+#pragma unroll
+        for (int r = 0; r < NO; ++r) {
+          if (!((uint32_t)r < p)) continue;
+          const Gf8Tab t = read_tab(tq, tt2, lb + r * kc + i0 + j);
+#pragma unroll
+          for (int w = 0; w < NW; ++w) acc[r][w] = gf8_mac4(acc[r][w], t, sel[w]);
+        }
+        // as gf8_span: keep the XOR chains from being reassociated into a tree
+#pragma unroll
+        for (int r = 0; r < NO; ++r)
+#pragma unroll
+          for (int w = 0; w < NW; ++w) pin(acc[r][w]);
+      }
+    }
+  }
+  uint32_t any = 0u;
+  const uint8_t* par = sbase + (uint64_t)k * a.shard_bytes + off;
+#pragma unroll
+  for (int r = 0; r < NO; ++r) {
+    if (!((uint32_t)r < p)) continue;
+    uint32_t x[NW];
+    loc_load<NW>(par + (uint64_t)r * a.shard_bytes, valid, x);
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+      acc[r][w] ^= x[w];
+      any |= acc[r][w];
+    }
+  }
+  if (__ballot(any != 0u) == 0ull) return;
+  if (any != 0u) slow(acc, sbase, off);
+}
+
+// The sweep of one stripe by one workgroup: its units of 256 lanes, 16-byte
+// vectors first, then the byte-wise part.
+template <int NO, bool MULTI, class Slow>
+__device__ __forceinline__ void loc_sweep(const LocateArgs& a, uint4* tq, uint32_t* tt2,
+                                          const uint8_t* sbase, const Slow& slow) {
+  const uint64_t n_vspans = (a.n_vec + kLocBlock - 1) / kLocBlock;
+  const uint64_t tail0 = a.n_vec * 16u;  // first byte of the byte-wise part
+  const uint64_t n_units = n_vspans + (a.shard_bytes - tail0 + kLocBlock - 1) / kLocBlock;
+  for (uint64_t u = blockIdx.x; u < n_units; u += gridDim.x) {
+    if (u < n_vspans) {
+      const uint64_t v = u * kLocBlock + threadIdx.x;
+      loc_unit<NO, 4, MULTI>(a, tq, tt2, sbase, v * 16u, v < a.n_vec, slow);
+    } else {
+      const uint64_t b = tail0 + (u - n_vspans) * kLocBlock + threadIdx.x;
+      loc_unit<NO, 1, MULTI>(a, tq, tt2, sbase, b, b < a.shard_bytes, slow);
+    }
+  }
+}
+
+// Vector width and grid of both passes.  16-byte vectors when every shard
+// starts on a 16-byte boundary.  A few workgroups per CU over the whole grid,
+// and at most four units per workgroup while that keeps the grid small: the
+// stripes that take the slow path are then spread over many CUs instead of
+// trailing the clean ones on eight workgroups each.
+inline dim3 loc_grid(LocateArgs& a) {
+  const bool al = (reinterpret_cast<uintptr_t>(a.base) % 16u) == 0 && a.shard_bytes % 16u == 0;
+  a.n_vec = al ? a.shard_bytes / 16u : 0;
+  const uint64_t units = (a.n_vec + kLocBlock - 1) / kLocBlock +
+                         (a.shard_bytes - a.n_vec * 16u + kLocBlock - 1) / kLocBlock;
+  const uint32_t gy = (uint32_t)(a.n_stripes < 65535u ? a.n_stripes : 65535u);
+  uint64_t gx = 4096u / gy;
+  if (gx < units / 4u) gx = units / 4u;
+  if (gx > 65536u / gy + 1u) gx = 65536u / gy + 1u;
+  if (gx < 1) gx = 1;
+  if (gx > units) gx = units;
+  return dim3((uint32_t)gx, gy);
+}
+
+}  // namespace locate_core
+}  // namespace rse

@@ -22,6 +22,10 @@ _lib = load()
 LOCATE_CLEAN = 0
 LOCATE_LOCATED = 1
 LOCATE_UNCORRECTABLE = 2
+# rse_correct_flat's per-stripe status (RSE_CORRECT_*)
+CORRECT_CLEAN = 0
+CORRECT_CORRECTED = 1
+CORRECT_UNCORRECTABLE = 2
 
 ShardList = Sequence[torch.Tensor]
 
@@ -370,6 +374,50 @@ class ReedSolomon:
         _raise(_lib.rse_locate_flat(self._h, base, shard_len, n_stripes, present.data_ptr(),
                                     status.data_ptr(), _stream(stripes)))
         return present[:n_stripes], status[:n_stripes]
+
+    def correct_flat(self, stripes: torch.Tensor, shard_len: int, n_stripes: int = 1,
+                     present=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """Repair the wrong bytes of every stripe of the flat layout in place
+        (rse_correct_flat): returns ``(status, changed, counts)``, device
+        tensors of shapes ``(n_stripes,)`` uint8, ``(n_stripes, k+p)`` uint8 and
+        ``(n_stripes, 2)`` int32.  ``status`` is CORRECT_CLEAN, CORRECT_CORRECTED
+        or CORRECT_UNCORRECTABLE; ``changed`` is 1 at the shards that had a byte
+        stored; ``counts`` holds {bytes stored, columns left undecodable}
+        (unsigned, saturating: view as uint32 past 2^31).  ``present``
+        (n_stripes x (k+p) flags, 0 = erased; None: nothing erased) names
+        known-missing shards, whose contents are arbitrary: a host array is
+        uploaded, a device tensor -- locate_flat()'s, say -- is read in place.
+        Every byte column is decoded on its own: with f erased shards, nu wrong
+        ones are repaired when 2 nu + f <= p; an undecodable column is left as
+        it was while the stripe's other columns are still repaired; a stripe
+        with f > p is not touched.  Queued on the current stream, no
+        synchronisation.  Same codecs as locate_flat(); confirm with
+        verify_flat()."""
+        T = self.total_shard_count()
+        _check_flat(stripes, shard_len, n_stripes, T, self.field)
+        base = _dev(stripes)
+        pres = None
+        if present is not None:
+            if isinstance(present, torch.Tensor) and present.is_cuda:
+                pres = present  # read in place, on that device
+            else:
+                flags = np.ascontiguousarray(np.asarray(
+                    present.cpu() if isinstance(present, torch.Tensor) else present, dtype=bool))
+                pres = torch.from_numpy(flags.view(np.uint8)).to(stripes.device)
+            if (tuple(pres.shape) != (n_stripes, T) or not pres.is_contiguous()
+                    or pres.dtype not in (torch.bool, torch.uint8)
+                    or pres.device != stripes.device):
+                raise RSError(Error.InvalidShardFlags)
+        # at least one row: an empty tensor has no address to pass
+        rows = max(1, n_stripes)
+        status = torch.empty((rows,), dtype=torch.uint8, device=stripes.device)
+        changed = torch.empty((rows, T), dtype=torch.uint8, device=stripes.device)
+        counts = torch.empty((rows, 2), dtype=torch.int32, device=stripes.device)
+        _raise(_lib.rse_correct_flat(self._h, base, shard_len, n_stripes,
+                                     pres.data_ptr() if pres is not None and n_stripes else None,
+                                     status.data_ptr(), changed.data_ptr(), counts.data_ptr(),
+                                     _stream(stripes)))
+        return status[:n_stripes], changed[:n_stripes], counts[:n_stripes]
 
     def reconstruct_data_flat(self, stripes: torch.Tensor, shard_len: int, n_stripes: int,
                               present: Sequence[bool]) -> None:
