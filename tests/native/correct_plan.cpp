@@ -5,7 +5,10 @@
 //    shards, f erased shards): the codeword, the received column (erased
 //    shards hold arbitrary bytes), both position sets and the decoder's result;
 //  - columns with errors and erasures at the ends of the point shift and at
-//    the limits of the capacity, for 10+4 and 239+16.
+//    the limits of the capacity, for 10+4 and 239+16;
+//  - a seeded grid inside the capacity for codecs of every parity count 6 .. 16
+//    (and 2+3): every (f, nu) with 2 nu + f <= p, checked here against the
+//    injection itself -- only a count and the failures are printed.
 // tests/test_correct_plan.py compares all of it with a brute-force model.
 //
 // Lines: "<tag> k p idx ..." with integers only.
@@ -43,26 +46,25 @@ struct Codec {
   }
 };
 
-// A random codeword with the shards `era` erased (arbitrary bytes in their
-// place) and the shards `err` made wrong, decoded as the kernel does: a stripe
-// with more than p erasures is skipped, a column with d = P data ^ parity = 0
-// is left alone, any other goes through S = T d and the column decoder.
-static void column(const Codec& c, size_t idx, const std::vector<uint32_t>& era,
-                   const std::vector<uint32_t>& err) {
-  const LocatePlan& pl = c.pl;
-  const uint32_t k = pl.k, p = pl.p, n = pl.n;
-  std::vector<uint8_t> col(n, 0);
+// A random codeword of the codec
+static std::vector<uint8_t> codeword(const LocatePlan& pl) {
+  const uint32_t k = pl.k, p = pl.p;
+  std::vector<uint8_t> col(pl.n, 0);
   for (uint32_t i = 0; i < k; ++i) col[i] = (uint8_t)rnd();
   for (uint32_t r = 0; r < p; ++r)
     for (uint32_t i = 0; i < k; ++i) col[k + r] ^= Gf8::mul(pl.P[(size_t)r * k + i], col[i]);
-  print_row("cw", pl, idx, col.data(), n);
-  for (uint32_t q : era) col[q] = (uint8_t)rnd();
-  for (uint32_t q : err) col[q] ^= (uint8_t)(1u + rnd() % 255u);
-  print_row("rx", pl, idx, col.data(), n);
-  std::vector<uint8_t> e8(era.begin(), era.end()), i8(err.begin(), err.end());
-  print_row("era", pl, idx, e8.data(), e8.size());
-  print_row("inj", pl, idx, i8.data(), i8.size());
+  return col;
+}
 
+// The received column `col` with the shards `era` erased, decoded in place as
+// the kernel does: a stripe with more than p erasures is skipped, a column
+// with d = P data ^ parity = 0 is left alone, any other goes through S = T d
+// and the column decoder.  Returns the decoder's m (0 for a column left alone),
+// kLocateBad for an undecodable column.
+static uint32_t decode(const Codec& c, std::vector<uint8_t>& col,
+                       const std::vector<uint32_t>& era) {
+  const LocatePlan& pl = c.pl;
+  const uint32_t k = pl.k, p = pl.p, n = pl.n;
   const uint8_t* lg = c.consts.data() + rse::kLocLogOff;
   const uint8_t* ex = c.consts.data() + rse::kLocExpOff;
   uint8_t epos[16] = {0};
@@ -83,7 +85,6 @@ static void column(const Codec& c, size_t idx, const std::vector<uint32_t>& era,
     rse::pk_set(d, r, v);
     any = any || v != 0;
   }
-  std::vector<uint8_t> res;
   uint32_t m = 0;
   if (f > p) {
     m = rse::kLocateBad;
@@ -91,11 +92,29 @@ static void column(const Codec& c, size_t idx, const std::vector<uint32_t>& era,
     rse::locate_syndromes(lg, ex, c.consts.data() + rse::kLocTOff, d, p, S);
     m = rse::correct_column(lg, ex, c.consts.data() + rse::kCorInvUOff, S, p, n, er, pos, val);
   }
-  res.push_back((uint8_t)m);  // 255: undecodable
-  if (m != rse::kLocateBad) {
+  if (m != rse::kLocateBad)
     for (uint32_t i = 0; i < m; ++i) col[rse::pk_get(pos, i)] ^= (uint8_t)rse::pk_get(val, i);
-    res.insert(res.end(), col.begin(), col.end());
-  }
+  return m;
+}
+
+// A random codeword with the shards `era` erased (arbitrary bytes in their
+// place) and the shards `err` made wrong, decoded and printed.
+static void column(const Codec& c, size_t idx, const std::vector<uint32_t>& era,
+                   const std::vector<uint32_t>& err) {
+  const LocatePlan& pl = c.pl;
+  const uint32_t n = pl.n;
+  std::vector<uint8_t> col = codeword(pl);
+  print_row("cw", pl, idx, col.data(), n);
+  for (uint32_t q : era) col[q] = (uint8_t)rnd();
+  for (uint32_t q : err) col[q] ^= (uint8_t)(1u + rnd() % 255u);
+  print_row("rx", pl, idx, col.data(), n);
+  std::vector<uint8_t> e8(era.begin(), era.end()), i8(err.begin(), err.end());
+  print_row("era", pl, idx, e8.data(), e8.size());
+  print_row("inj", pl, idx, i8.data(), i8.size());
+  const uint32_t m = decode(c, col, era);
+  std::vector<uint8_t> res;
+  res.push_back((uint8_t)m);  // 255: undecodable
+  if (m != rse::kLocateBad) res.insert(res.end(), col.begin(), col.end());
   print_row("res", pl, idx, res.data(), res.size());
 }
 
@@ -139,11 +158,43 @@ static void edges(uint32_t k, uint32_t p, uint64_t seed) {
   column(c, 100011, {}, {});
 }
 
+// Inside the capacity the decoded column is the codeword it was made from:
+// kGridCols seeded columns for every (f, nu) with 2 nu + f <= p.  Prints
+// "gridfail k p idx f nu" per column that is not, then "grid k p 0 columns
+// failures".
+constexpr int kGridCols = 40;
+static void grid(uint32_t k, uint32_t p, uint64_t seed) {
+  const Codec c(k, p);
+  const uint32_t n = c.pl.n;
+  g_rng = seed * 0x9E3779B97F4A7C15ull + k * 131u + p;
+  size_t idx = 0, fails = 0;
+  for (uint32_t f = 0; f <= p; ++f)
+    for (uint32_t nu = 0; 2 * nu + f <= p; ++nu)
+      for (int q = 0; q < kGridCols; ++q, ++idx) {
+        const std::vector<uint32_t> all = pick(n, nu + f);
+        const std::vector<uint32_t> era(all.begin(), all.begin() + f);
+        const std::vector<uint8_t> cw = codeword(c.pl);
+        std::vector<uint8_t> col = cw;
+        for (uint32_t s : era) col[s] = (uint8_t)rnd();
+        for (uint32_t i = f; i < nu + f; ++i) col[all[i]] ^= (uint8_t)(1u + rnd() % 255u);
+        const uint32_t m = decode(c, col, era);
+        if (m == rse::kLocateBad || m > p || col != cw) {
+          const uint8_t fn[2] = {(uint8_t)f, (uint8_t)nu};
+          print_row("gridfail", c.pl, idx, fn, 2);
+          ++fails;
+        }
+      }
+  std::printf("grid %u %u 0 %zu %zu\n", k, p, idx, fails);
+}
+
 int main(int argc, char** argv) {
   // The default seed was chosen on the CPU so that the columns past capacity
   // hold both outcomes for every codec (tests/test_correct_plan.py).
   const uint64_t seed = argc > 1 ? std::strtoull(argv[1], nullptr, 0) : 1;
-  const uint32_t plans[][2] = {{10, 4}, {3, 2}, {4, 5}, {17, 3}, {1, 1}, {100, 16}, {239, 16}};
+  const uint32_t plans[][2] = {{10, 4}, {3, 2},  {4, 5},   {17, 3},  {1, 1},    {100, 16},
+                               {239, 16}, {20, 8}, {6, 9},   {30, 15},  {12, 12},  {5, 6},
+                               {7, 7},    {40, 10}, {200, 11}, {50, 13}, {60, 14}, {1, 16},
+                               {128, 16}, {129, 16}, {2, 3}};
   for (auto& kp : plans) {
     const Codec c(kp[0], kp[1]);
     print_row("iu", c.pl, 0, c.consts.data() + rse::kCorInvUOff, c.pl.n);
@@ -173,5 +224,11 @@ int main(int argc, char** argv) {
 
   edges(10, 4, seed + 1);
   edges(239, 16, seed + 2);
+
+  // every parity count 6 .. 16, single-chunk and multi-chunk k, k = 1
+  const uint32_t wide[][2] = {{20, 8},  {6, 9},   {30, 15}, {12, 12},  {5, 6},    {7, 7},
+                              {40, 10}, {200, 11}, {50, 13}, {60, 14},  {1, 16},   {128, 16},
+                              {129, 16}, {100, 16}, {239, 16}, {2, 3}};
+  for (auto& kp : wide) grid(kp[0], kp[1], seed);
   return 0;
 }

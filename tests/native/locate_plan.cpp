@@ -4,11 +4,15 @@
 //  - seeded byte columns with 0 .. p wrong shards for three small codecs: the
 //    received column, the injected positions and the decoder's verdict;
 //  - columns with errors at the ends of the point shift (shard 0, shard n-1,
-//    and shard 254 of 239+16).
+//    and shard 254 of 239+16);
+//  - a seeded grid of 0 .. t wrong shards for codecs of every parity count
+//    6 .. 16, checked here against the injection itself -- only a count and the
+//    failures are printed.
 // tests/test_locate_plan.py compares all of it with the oracle's matrices and
 // a brute-force statement of what "decodable" means.
 //
 // Lines: "<tag> k p ..." with integers only.
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -80,11 +84,54 @@ static std::vector<uint32_t> pick(uint32_t n, uint32_t count) {
   return all;
 }
 
+// With at most t wrong shards the decoder names exactly those, ascending:
+// kGridCols seeded columns for every count 0 .. t.  Prints "gridfail k p idx
+// nu" per column where it does not, then "grid k p 0 columns failures".
+constexpr int kGridCols = 40;
+static void grid(uint32_t k, uint32_t p, uint64_t seed) {
+  const LocatePlan pl = rse::make_locate_plan(k, p);
+  std::vector<uint8_t> consts(rse::locate_consts_bytes(pl));
+  rse::locate_consts(pl, consts.data());
+  const uint8_t* lg = consts.data() + rse::kLocLogOff;
+  const uint8_t* ex = consts.data() + rse::kLocExpOff;
+  g_rng = seed * 0x9E3779B97F4A7C15ull + k * 131u + p;
+  size_t idx = 0, fails = 0;
+  for (uint32_t nu = 0; nu <= pl.t; ++nu)
+    for (int q = 0; q < kGridCols; ++q, ++idx) {
+      std::vector<uint32_t> pos = pick(pl.n, nu);
+      std::vector<uint8_t> col(pl.n, 0);
+      for (uint32_t i = 0; i < k; ++i) col[i] = (uint8_t)rnd();
+      for (uint32_t r = 0; r < p; ++r)
+        for (uint32_t i = 0; i < k; ++i) col[k + r] ^= Gf8::mul(pl.P[(size_t)r * k + i], col[i]);
+      for (uint32_t s : pos) col[s] ^= (uint8_t)(1u + rnd() % 255u);
+      uint32_t d[4] = {0, 0, 0, 0}, S[4], roots[2];
+      for (uint32_t r = 0; r < p; ++r) {
+        uint8_t v = col[k + r];
+        for (uint32_t i = 0; i < k; ++i) v ^= Gf8::mul(pl.P[(size_t)r * k + i], col[i]);
+        rse::pk_set(d, r, v);
+      }
+      rse::locate_syndromes(lg, ex, consts.data() + rse::kLocTOff, d, p, S);
+      const uint32_t L = rse::locate_column(lg, ex, S, p, pl.n, roots);
+      std::sort(pos.begin(), pos.end());
+      bool ok = L == nu;
+      for (uint32_t i = 0; ok && i < nu; ++i) ok = rse::pk_get(roots, i) == pos[i];
+      if (!ok) {
+        const uint8_t b = (uint8_t)nu;
+        print_row("gridfail", pl, idx, &b, 1);
+        ++fails;
+      }
+    }
+  std::printf("grid %u %u 0 %zu %zu\n", k, p, idx, fails);
+}
+
 int main(int argc, char** argv) {
   // The default seed was chosen on the CPU so that the columns with more than
   // t wrong shards hold both outcomes (tests/test_locate_plan.py).
   const uint64_t seed = argc > 1 ? std::strtoull(argv[1], nullptr, 0) : 4;
-  const uint32_t plans[][2] = {{10, 4}, {3, 2}, {4, 5}, {17, 3}, {1, 1}, {100, 16}, {239, 16}};
+  const uint32_t plans[][2] = {{10, 4}, {3, 2},  {4, 5},   {17, 3},  {1, 1},    {100, 16},
+                               {239, 16}, {20, 8}, {6, 9},   {30, 15},  {12, 12},  {5, 6},
+                               {7, 7},    {40, 10}, {200, 11}, {50, 13}, {60, 14}, {1, 16},
+                               {128, 16}, {129, 16}, {2, 3}};
   for (auto& kp : plans) {
     if (!rse::locate_in_scope(8, kp[0], kp[1])) return 1;
     print_plan(rse::make_locate_plan(kp[0], kp[1]));
@@ -126,5 +173,11 @@ int main(int argc, char** argv) {
     column(pl, consts.data(), 1003, {0, 1, 100, 238, 239, 240, 253, 254});
     column(pl, consts.data(), 1004, {});
   }
+
+  // every parity count 6 .. 16, single-chunk and multi-chunk k, k = 1
+  const uint32_t wide[][2] = {{20, 8},  {6, 9},   {30, 15}, {12, 12},  {5, 6},    {7, 7},
+                              {40, 10}, {200, 11}, {50, 13}, {60, 14},  {1, 16},   {128, 16},
+                              {129, 16}, {100, 16}, {239, 16}, {2, 3}};
+  for (auto& kp : wide) grid(kp[0], kp[1], seed);
   return 0;
 }

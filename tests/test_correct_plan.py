@@ -13,7 +13,11 @@ Berlekamp-Massey):
 - past that capacity both outcomes occur: undecodable columns, and columns
   decoded to ANOTHER codeword (the inherent limit);
 - the ends of the point shift (shards 0, n-1, 254) and the limits of the
-  capacity on 10+4 and 239+16.
+  capacity on 10+4 and 239+16;
+- for codecs of every parity count 6 .. 16 (NO = 8 and NO = 16 of the kernel,
+  full and partly filled) a seeded grid of every (f, nu) with 2 nu + f <= p:
+  the decoded column is the codeword the column was made from.  The expected
+  value is the injection's, checked in the program; it prints only failures.
 
 The same program also runs under ASan + UBSan (host code only)."""
 import os
@@ -31,7 +35,12 @@ import correct_model as CM  # noqa: E402
 
 CSRC = os.path.join(HERE, "..", "reed-solomon-erasure_amd", "csrc")
 SRC = os.path.join(HERE, "native", "correct_plan.cpp")
-PLANS = [(10, 4), (3, 2), (4, 5), (17, 3), (1, 1), (100, 16), (239, 16)]
+# every parity count 6 .. 16 (and 3): k = 1, one chunk of the kernel's tables
+# (k <= 128 at p > 8) and more than one, the widest codec
+GRID = [(20, 8), (6, 9), (30, 15), (12, 12), (5, 6), (7, 7), (40, 10), (200, 11), (50, 13),
+        (60, 14), (1, 16), (128, 16), (129, 16), (100, 16), (239, 16), (2, 3)]
+PLANS = [(10, 4), (3, 2), (4, 5), (17, 3), (1, 1)] + GRID
+GRID_COLS = 40  # per group, as tests/native/correct_plan.cpp
 SMALL = [(3, 2), (6, 4), (4, 5)]
 BAD = 255
 
@@ -139,6 +148,13 @@ def test_edges(walk, k, p):
         if len(inj) <= 1:  # the model's search stays small: nu <= 1
             assert got == CM.correct_column(hc, rx, era, p), idx
     assert cases[100009][4] is None  # more erasures than checks
+
+
+@pytest.mark.parametrize("k,p", GRID)
+def test_grid_inside_capacity_decodes_to_the_codeword(walk, k, p):
+    groups = sum(1 for f in range(p + 1) for nu in range(p + 1) if 2 * nu + f <= p)
+    assert ("gridfail", k, p) not in walk, sorted(walk[("gridfail", k, p)].items())[:8]
+    assert walk[("grid", k, p)][0] == [GRID_COLS * groups, 0]
 
 
 def test_walk_is_clean_under_sanitizers(tmp_path, walk):

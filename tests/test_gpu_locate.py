@@ -12,6 +12,7 @@ are allocated with one spare row past the batch, filled with 0xA5, which must
 keep it.  Shard lengths: 1, 15, 17 and 4096 + 37 (byte-wise path: the shards
 of a flat stripe of odd length start at odd addresses), 4096 (16-byte
 vectors, whole spans) and 4096 + 16 (a partly filled span); 65537 for 10+4.
+20+8, 6+9, 30+15, 128+16 and 129+16 run at 17 and 4096 + 16 only.
 """
 
 import numpy as np
@@ -29,7 +30,12 @@ pytestmark = pytest.mark.gpu
 LIB = load()
 CODECS = [(10, 4), (3, 2), (4, 5), (17, 3), (1, 1), (100, 16), (239, 16)]
 LENGTHS = [1, 15, 17, 4096, 4096 + 16, 4096 + 37]
-CASES = [(k, p, n) for k, p in CODECS for n in LENGTHS] + [(10, 4, 65537)]
+# parity counts 8, 9 and 15, and k on both sides of one chunk of the kernels'
+# tables at p = 16: a byte-wise and a vector length each
+WIDE_CODECS = [(20, 8), (6, 9), (30, 15), (128, 16), (129, 16)]
+WIDE_LENGTHS = [17, 4096 + 16]
+CASES = [(k, p, n) for k, p in CODECS for n in LENGTHS] + [(10, 4, 65537)] + \
+        [(k, p, n) for k, p in WIDE_CODECS for n in WIDE_LENGTHS]
 NS = 5
 CLEAN, LOCATED, UNCORRECTABLE = 0, 1, 2
 

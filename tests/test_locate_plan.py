@@ -12,7 +12,11 @@ decoder is the very code the kernel runs -- and compared with the oracle:
 - columns with more than t wrong shards: decoder and model agree, and both
   outcomes occur -- undecodable columns, and columns within t of ANOTHER
   codeword (the inherent limit: innocent shards are named);
-- errors at the ends of the point shift: shard 0, shard n-1, shard 254.
+- errors at the ends of the point shift: shard 0, shard n-1, shard 254;
+- for codecs of every parity count 6 .. 16 a seeded grid of 0 .. t wrong
+  shards: the decoder names exactly the injected shards, ascending.  The
+  expected value is the injection's, checked in the program; it prints only
+  failures.
 
 The same program also runs under ASan + UBSan (host code only)."""
 import os
@@ -29,7 +33,12 @@ import locate_model as LM  # noqa: E402
 
 CSRC = os.path.join(HERE, "..", "reed-solomon-erasure_amd", "csrc")
 SRC = os.path.join(HERE, "native", "locate_plan.cpp")
-PLANS = [(10, 4), (3, 2), (4, 5), (17, 3), (1, 1), (100, 16), (239, 16)]
+# every parity count 6 .. 16 (and 3): k = 1, one chunk of the kernel's tables
+# (k <= 128 at p > 8) and more than one, the widest codec
+GRID = [(20, 8), (6, 9), (30, 15), (12, 12), (5, 6), (7, 7), (40, 10), (200, 11), (50, 13),
+        (60, 14), (1, 16), (128, 16), (129, 16), (100, 16), (239, 16), (2, 3)]
+PLANS = [(10, 4), (3, 2), (4, 5), (17, 3), (1, 1)] + GRID
+GRID_COLS = 40  # per group, as tests/native/locate_plan.cpp
 SMALL = [(3, 2), (6, 4), (4, 5)]
 BAD = 255
 
@@ -136,6 +145,12 @@ def test_edge_positions(walk):
             assert walk[("inj", k, p)][idx] == want
             res = walk[("res", k, p)][idx]
             assert res[0] == len(want) and sorted(res[1:]) == want, (k, p, idx, res)
+
+
+@pytest.mark.parametrize("k,p", GRID)
+def test_grid_up_to_t_wrong_shards_are_named(walk, k, p):
+    assert ("gridfail", k, p) not in walk, sorted(walk[("gridfail", k, p)].items())[:8]
+    assert walk[("grid", k, p)][0] == [GRID_COLS * (p // 2 + 1), 0]
 
 
 def test_walk_is_clean_under_sanitizers(tmp_path, walk):
