@@ -66,6 +66,44 @@ struct Rows {
   uint16_t at(size_t r, size_t i) const { return c[r * n_in + i]; }
 };
 
+// Constants a codec keeps on every device that uses them, for its life: made
+// on the first use there, with a synchronous copy (that call pays it; every
+// later one is asynchronous); two threads racing keep one copy and free the
+// other.
+class DevConsts {
+ public:
+  ~DevConsts() {
+    for (auto& a : slot_)
+      if (uint8_t* q = a.load()) (void)hipFree(q);
+  }
+  // build(): the host bytes (a std::vector<uint8_t>), called when `dev` has no copy yet
+  template <class Build>
+  hipError_t get(int dev, const Build& build, const uint8_t** out) {
+    if (dev < 0 || dev >= kDevs) return hipErrorInvalidDevice;
+    uint8_t* q = slot_[dev].load(std::memory_order_acquire);
+    if (!q) {
+      const std::vector<uint8_t> h = build();
+      hipError_t e = hipMalloc(reinterpret_cast<void**>(&q), h.size());
+      if (e == hipSuccess) e = hipMemcpy(q, h.data(), h.size(), hipMemcpyHostToDevice);
+      if (e != hipSuccess) {
+        if (q) (void)hipFree(q);
+        return e;
+      }
+      uint8_t* expect = nullptr;
+      if (!slot_[dev].compare_exchange_strong(expect, q, std::memory_order_acq_rel)) {
+        (void)hipFree(q);
+        q = expect;
+      }
+    }
+    *out = q;
+    return hipSuccess;
+  }
+
+ private:
+  static constexpr int kDevs = 64;
+  std::atomic<uint8_t*> slot_[kDevs] = {};
+};
+
 }  // namespace
 
 struct rse_codec {
@@ -100,17 +138,10 @@ struct rse_codec {
   // the device planners' GF(2^8) tables (rse::plan_tables), made on the first
   // batched reconstruct there and kept for the codec's life (plan_consts), so
   // a call copies neither.
-  static constexpr int kDevs = 64;
-  mutable std::atomic<uint8_t*> plan_dev[kDevs] = {};
+  mutable DevConsts plan_dev;
   // Per device: rse_locate_flat's plan (rse_locate_plan.hpp locate_consts),
   // made on the first locate there and kept likewise (locate_plan_consts).
-  mutable std::atomic<uint8_t*> locate_dev[kDevs] = {};
-  ~rse_codec() {
-    for (auto& a : plan_dev)
-      if (uint8_t* q = a.load()) (void)hipFree(q);
-    for (auto& a : locate_dev)
-      if (uint8_t* q = a.load()) (void)hipFree(q);
-  }
+  mutable DevConsts locate_dev;
 
   size_t esize() const { return field == 16 ? 2 : 1; }
   uint16_t mat(size_t r, size_t c) const { return field == 16 ? m16.at(r, c) : m8.at(r, c); }
@@ -241,10 +272,38 @@ bool bitslice_len(size_t len) {
   return len >= 4096 || ((len == 1024 || len == 2048) && rse::get_option(RSE_OPT_SUB_CHUNKS));
 }
 
+// Is every pointer the job's mode touches 16-byte aligned?
+bool job_aligned16(const Job& j) {
+  bool al = true;
+  for (size_t i = 0; i < j.rows->n_in; ++i) al = al && aligned16(j.in[i]);
+  for (size_t r = 0; r < j.rows->n_out; ++r) {
+    if (j.mode != rse::kCheck) al = al && aligned16(j.out[r]);
+    if (j.mode != rse::kStore) al = al && aligned16(j.cmp[r]);
+  }
+  return al;
+}
+
+// What every kernel that codes whole chunks of the shards asks of a job
+// (run_job), before anything that looks at its rows.
+bool chunk_kernels_open(const Job& j) {
+  return !j.accumulate && j.stripe_stride % 16u == 0 && rse::get_option(RSE_OPT_BITSLICE) &&
+         j.n_stripes <= 0xffffffffu;
+}
+
+// Runs rest() after a launch that coded the first bytes of every shard; that
+// launch stays the kernel rse_last_kernel reports.
+template <class Rest>
+int rest_after_kernel(const Rest& rest) {
+  const std::string first = rse::last_kernel();  // the launch to report
+  const int rc = rest();
+  rse::note_kernel("%s", first.c_str());
+  return rc;
+}
+
 int run_job(const Job& j, hipStream_t s);
 
 // The bytes of every shard past `done` (a wide launch coded whole chunks up
-// to there); the wide launch stays the kernel rse_last_kernel reports.
+// to there).
 int run_rest(const Job& j, uint64_t done, hipStream_t s) {
   const size_t n_out = j.rows->n_out, n_in = j.rows->n_in;
   std::vector<const uint8_t*> in(j.in, j.in + n_in);
@@ -260,10 +319,7 @@ int run_rest(const Job& j, uint64_t done, hipStream_t s) {
   rest.out = j.out ? out.data() : nullptr;
   rest.cmp = j.cmp ? cmp.data() : nullptr;
   rest.len_bytes = j.len_bytes - done;
-  const std::string wide_kernel = rse::last_kernel();  // the launch to report
-  const int rc = run_job(rest, s);
-  rse::note_kernel("%s", wide_kernel.c_str());
-  return rc;
+  return rest_after_kernel([&] { return run_job(rest, s); });
 }
 
 // Executes a Job; `scratch` provides per-output buffers when a CHECK job must
@@ -283,85 +339,46 @@ int run_job(const Job& j, hipStream_t s) {
       return run_job(g, s);
     }
   }
-  // GF(2^8) k = p = 16 / 32 / 64 (RSE_OPT_FFT 2: and 128): the codec's parity rows (encode, verify; also
-  // their own inverse, so all data shards rebuilt from the parity) on the
-  // additive-FFT kernels (rse_fft.hip): every whole 2 KiB column (1 KiB shards: all), the
-  // rest of every shard below
-  if (!j.accumulate && j.field == RSE_FIELD_GF8 && n_in == n_out && j.stripe_stride % 16u == 0 &&
-      rse::get_option(RSE_OPT_BITSLICE) && j.n_stripes <= 0xffffffffu &&
-      rse::fft_applies(8, (uint32_t)n_in, (uint32_t)n_out, j.rows->c.data())) {
-    bool al = true;
-    for (size_t i = 0; i < n_in; ++i) al = al && aligned16(j.in[i]);
-    for (size_t r = 0; r < n_out; ++r) {
-      if (j.mode != rse::kCheck) al = al && aligned16(j.out[r]);
-      if (j.mode != rse::kStore) al = al && aligned16(j.cmp[r]);
-    }
-    uint64_t done = 0;
-    if (al)
-      RSE_HIP(rse::launch_fft(j.field, (uint32_t)n_in, (uint32_t)n_out, j.rows->c.data(), j.in,
-                              j.out, j.cmp, j.len_bytes, j.stripe_stride, (uint32_t)j.n_stripes,
-                              j.mode, j.mismatch, j.per_stripe, s, &done));
-    if (done) return done == j.len_bytes ? RSE_OK : run_rest(j, done, s);
-  }
-  // a wide codec's (or pattern's) rows with their one-module kernel built:
-  // every whole 4 KiB chunk in one launch (each input read once, each output
-  // written once), the rest of every shard below
-  if (!j.accumulate && bitslice_len(j.len_bytes) && j.stripe_stride % 16u == 0 &&
-      rse::get_option(RSE_OPT_BITSLICE) && rse::wide_eligible((uint32_t)n_in, (uint32_t)n_out) &&
-      j.n_stripes <= 0xffffffffu) {
-    bool al = true;
-    for (size_t i = 0; i < n_in; ++i) al = al && aligned16(j.in[i]);
-    for (size_t r = 0; r < n_out; ++r) {
-      if (j.mode != rse::kCheck) al = al && aligned16(j.out[r]);
-      if (j.mode != rse::kStore) al = al && aligned16(j.cmp[r]);
-    }
-    uint64_t done = 0;
-    if (al)
-      RSE_HIP(rse::launch_wide(j.field, (uint32_t)n_in, (uint32_t)n_out, j.rows->c.data(), j.in,
-                               j.out, j.cmp, j.len_bytes, j.stripe_stride, (uint32_t)j.n_stripes,
-                               j.mode, j.mismatch, j.per_stripe, s, &done));
-    if (done) return done == j.len_bytes ? RSE_OK : run_rest(j, done, s);
-  }
-  // RSE_OPT_FFT16: a GF(2^16) codec past 256 shards with 2^m - k <= 32, its
-  // parity rows (encode, verify) on the pruned-FFT kernel (rse_fft16.hip):
-  // every whole 4 KiB column, the rest of every shard below
-  if (!j.accumulate && j.field == RSE_FIELD_GF16 && j.len_bytes >= 4096 &&
-      j.stripe_stride % 16u == 0 && rse::get_option(RSE_OPT_BITSLICE) &&
-      j.n_stripes <= 0xffffffffu &&
-      rse::fft16_applies(16, (uint32_t)n_in, (uint32_t)n_out, j.rows->c.data())) {
-    bool al = true;
-    for (size_t i = 0; i < n_in; ++i) al = al && aligned16(j.in[i]);
-    for (size_t r = 0; r < n_out; ++r) {
-      if (j.mode != rse::kCheck) al = al && aligned16(j.out[r]);
-      if (j.mode != rse::kStore) al = al && aligned16(j.cmp[r]);
-    }
-    uint64_t done = 0;
-    if (al) {
-      const rse::Fft16Plan* fp = rse::fft16_plan(16, (uint32_t)n_in, (uint32_t)n_out);
+  // Whole chunks of every shard on one of the four kernels below, the rest of
+  // every shard on the others (run_rest).  They are tried in this order; one
+  // that launches nothing (its module is not built yet, the shards are shorter
+  // than its chunk) leaves `done` 0 and the job to the next.
+  uint64_t done = 0;
+  if (chunk_kernels_open(j) && job_aligned16(j)) {
+    const uint32_t ni = (uint32_t)n_in, no = (uint32_t)n_out, ns = (uint32_t)j.n_stripes;
+    const uint16_t* rows = j.rows->c.data();
+    // GF(2^8) k = p = 16 / 32 / 64 (RSE_OPT_FFT 2: and 128): the codec's parity rows (encode, verify; also
+    // their own inverse, so all data shards rebuilt from the parity) on the
+    // additive-FFT kernels (rse_fft.hip): every whole 2 KiB column (1 KiB shards: all)
+    if (j.field == RSE_FIELD_GF8 && n_in == n_out && rse::fft_applies(8, ni, no, rows))
+      RSE_HIP(rse::launch_fft(j.field, ni, no, rows, j.in, j.out, j.cmp, j.len_bytes,
+                              j.stripe_stride, ns, j.mode, j.mismatch, j.per_stripe, s, &done));
+    // a wide codec's (or pattern's) rows with their one-module kernel built:
+    // every whole 4 KiB chunk in one launch (each input read once, each output
+    // written once)
+    if (!done && bitslice_len(j.len_bytes) && rse::wide_eligible(ni, no))
+      RSE_HIP(rse::launch_wide(j.field, ni, no, rows, j.in, j.out, j.cmp, j.len_bytes,
+                               j.stripe_stride, ns, j.mode, j.mismatch, j.per_stripe, s, &done));
+    // RSE_OPT_FFT16: a GF(2^16) codec past 256 shards with 2^m - k <= 32, its
+    // parity rows (encode, verify) on the pruned-FFT kernel (rse_fft16.hip):
+    // every whole 4 KiB column (whatever RSE_OPT_SUB_CHUNKS says)
+    if (!done && j.field == RSE_FIELD_GF16 && j.len_bytes >= 4096 &&
+        rse::fft16_applies(16, ni, no, rows)) {
+      const rse::Fft16Plan* fp = rse::fft16_plan(16, ni, no);
       std::vector<const uint8_t*> in(fp->n, nullptr);
       std::copy(j.in, j.in + n_in, in.begin());
-      RSE_HIP(rse::launch_fft16(*fp, in.data(), (uint32_t)n_out, fp->enc.data(), j.out, j.cmp,
-                                j.len_bytes, j.stripe_stride, (uint32_t)j.n_stripes, j.mode,
-                                j.mismatch, j.per_stripe, j.mode == rse::kStore ? "code" : "check",
-                                s, &done));
+      RSE_HIP(rse::launch_fft16(*fp, in.data(), no, fp->enc.data(), j.out, j.cmp, j.len_bytes,
+                                j.stripe_stride, ns, j.mode, j.mismatch, j.per_stripe,
+                                j.mode == rse::kStore ? "code" : "check", s, &done));
     }
-    if (done) return done == j.len_bytes ? RSE_OK : run_rest(j, done, s);
+    // too wide for one module (GF(2^16) past 256 shards): the chain of wide
+    // modules over input blocks, once all of them are built (want_bitslice)
+    if (!done && j.mode == rse::kStore && bitslice_len(j.len_bytes) &&
+        rse::wide_blocks_plan(ni, no, nullptr))
+      RSE_HIP(rse::launch_wide_blocks(j.field, ni, no, rows, j.in, j.out, j.len_bytes,
+                                      j.stripe_stride, ns, s, &done));
   }
-  // too wide for one module (GF(2^16) past 256 shards): the chain of wide
-  // modules over input blocks, once all of them are built (want_bitslice)
-  if (j.mode == rse::kStore && !j.accumulate && bitslice_len(j.len_bytes) &&
-      j.stripe_stride % 16u == 0 && rse::get_option(RSE_OPT_BITSLICE) &&
-      j.n_stripes <= 0xffffffffu && rse::wide_blocks_plan((uint32_t)n_in, (uint32_t)n_out, nullptr)) {
-    bool al = true;
-    for (size_t i = 0; i < n_in; ++i) al = al && aligned16(j.in[i]);
-    for (size_t r = 0; r < n_out; ++r) al = al && aligned16(j.out[r]);
-    uint64_t done = 0;
-    if (al)
-      RSE_HIP(rse::launch_wide_blocks(j.field, (uint32_t)n_in, (uint32_t)n_out, j.rows->c.data(),
-                                      j.in, j.out, j.len_bytes, j.stripe_stride,
-                                      (uint32_t)j.n_stripes, s, &done));
-    if (done) return done == j.len_bytes ? RSE_OK : run_rest(j, done, s);
-  }
+  if (done) return done == j.len_bytes ? RSE_OK : run_rest(j, done, s);
   const bool single_in = n_in <= (size_t)kMaxIn;
   if (j.mode == rse::kStore || single_in) {
     // a wide codec's parity rows whose bit-sliced blocks are built (see
@@ -741,67 +758,45 @@ Rows parity_rows(const rse_codec* c) {  // core.rs:420-428
   return r;
 }
 
+// A caller's n_out x n_in coefficients (the low-level entries): one byte each,
+// GF(2^16) two, high byte first.
+Rows rows_from_bytes(int field, const uint8_t* rows, size_t n_out, size_t n_in) {
+  Rows r;
+  r.n_out = n_out;
+  r.n_in = n_in;
+  r.c.resize(n_out * n_in);
+  for (size_t i = 0; i < n_out * n_in; ++i)
+    r.c[i] = field == RSE_FIELD_GF16 ? (uint16_t)((rows[2 * i] << 8) | rows[2 * i + 1]) : rows[i];
+  return r;
+}
+
 // Byte offset of the planner tables in a codec's plan constants.
 size_t plan_tab_off(const rse_codec* c) { return (c->p * c->k * 2 + 255) & ~size_t(255); }
 
-// The codec's plan constants on device `dev` (rse_codec::plan_dev): made once
-// per device, with a synchronous copy (the first batched reconstruct there
-// pays it); two threads racing keep one copy and free the other.
+// The codec's plan constants on device `dev` (rse_codec::plan_dev; the first
+// batched reconstruct there pays the copy).
 hipError_t plan_consts(const rse_codec* c, int dev, const uint8_t** out) {
-  if (dev < 0 || dev >= rse_codec::kDevs) return hipErrorInvalidDevice;
-  if (uint8_t* q = c->plan_dev[dev].load(std::memory_order_acquire)) {
-    *out = q;
-    return hipSuccess;
-  }
-  const Rows r = parity_rows(c);
-  const size_t off = plan_tab_off(c);
-  std::vector<uint8_t> h(off + rse::kPlanTabBytes, 0);
-  std::memcpy(h.data(), r.c.data(), r.c.size() * 2);
-  rse::plan_tables(h.data() + off);
-  uint8_t* q = nullptr;
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(&q), h.size());
-  if (e == hipSuccess) e = hipMemcpy(q, h.data(), h.size(), hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    if (q) (void)hipFree(q);
-    return e;
-  }
-  uint8_t* expect = nullptr;
-  if (!c->plan_dev[dev].compare_exchange_strong(expect, q, std::memory_order_acq_rel)) {
-    (void)hipFree(q);
-    q = expect;
-  }
-  *out = q;
-  return hipSuccess;
+  return c->plan_dev.get(dev, [c] {
+    const Rows r = parity_rows(c);
+    const size_t off = plan_tab_off(c);
+    std::vector<uint8_t> h(off + rse::kPlanTabBytes, 0);
+    std::memcpy(h.data(), r.c.data(), r.c.size() * 2);
+    rse::plan_tables(h.data() + off);
+    return h;
+  }, out);
 }
 
-// The codec's locate plan on device `dev` (rse_codec::locate_dev), as
-// plan_consts: made once per device with a synchronous copy, which the first
-// rse_locate_flat there pays; every later call is asynchronous.
+// The codec's locate plan on device `dev` (rse_codec::locate_dev; the first
+// rse_locate_flat or rse_correct_flat there pays the copy).
 hipError_t locate_plan_consts(const rse_codec* c, int dev, const uint8_t** out) {
-  if (dev < 0 || dev >= rse_codec::kDevs) return hipErrorInvalidDevice;
-  if (uint8_t* q = c->locate_dev[dev].load(std::memory_order_acquire)) {
-    *out = q;
-    return hipSuccess;
-  }
-  const Rows r = parity_rows(c);
-  const rse::LocatePlan pl = rse::make_locate_plan(c->k, c->p, r.c.data());
-  // rse_locate_flat's layout, then what rse_correct_flat adds: one copy serves both
-  std::vector<uint8_t> h(rse::kCorConstsBytes, 0);
-  rse::correct_consts(pl, h.data());
-  uint8_t* q = nullptr;
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(&q), h.size());
-  if (e == hipSuccess) e = hipMemcpy(q, h.data(), h.size(), hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    if (q) (void)hipFree(q);
-    return e;
-  }
-  uint8_t* expect = nullptr;
-  if (!c->locate_dev[dev].compare_exchange_strong(expect, q, std::memory_order_acq_rel)) {
-    (void)hipFree(q);
-    q = expect;
-  }
-  *out = q;
-  return hipSuccess;
+  return c->locate_dev.get(dev, [c] {
+    const Rows r = parity_rows(c);
+    const rse::LocatePlan pl = rse::make_locate_plan(c->k, c->p, r.c.data());
+    // rse_locate_flat's layout, then what rse_correct_flat adds: one copy serves both
+    std::vector<uint8_t> h(rse::kCorConstsBytes, 0);
+    rse::correct_consts(pl, h.data());
+    return h;
+  }, out);
 }
 
 // Codecs without compiled-in bit-sliced kernels get them built for their
@@ -1150,8 +1145,7 @@ thread_local int64_t g_host_planned = 0;      // RSE_OPT_HOST_PLANNED_STRIPES
 // Shards of 4 KiB or more qualify, and of exactly 1 or 2 KiB (bitslice_len;
 // the SUB kernels).  Below 16 KiB the syndrome kernels code nothing (16 KiB
 // chunks), so without a pattern kernel such shards run on the table kernels.
-bool pattern_kernel(const rse_codec* c, const ReconPlan& plan, size_t len_bytes,
-                    size_t volume = 0) {
+bool pattern_kernel(const rse_codec* c, const ReconPlan& plan, size_t len_bytes, size_t volume) {
   const int64_t mode = rse::get_option(RSE_OPT_JIT);
   if (mode == 0 || !rse::get_option(RSE_OPT_JIT_PATTERNS) || !rse::get_option(RSE_OPT_BITSLICE) ||
       !bitslice_len(len_bytes) ||
@@ -1206,10 +1200,8 @@ int run_fft16_plan(const rse_codec* c, ReconPlan& plan, uint64_t stripe_stride,
                               (uint32_t)n_stripes, rse::kStore, nullptr, false, "rebuild", s, &done));
   if (done == len) return RSE_OK;
   rse::fft16_pattern_rows(*plan.fft16, plan.fft16_pattern, plan.rows.c);
-  const std::string kernel = done ? rse::last_kernel() : std::string();
-  const int rc = run_plan_tail(c, plan, done, stripe_stride, n_stripes, s);
-  if (done) rse::note_kernel("%s", kernel.c_str());
-  return rc;
+  const auto tail = [&] { return run_plan_tail(c, plan, done, stripe_stride, n_stripes, s); };
+  return done ? rest_after_kernel(tail) : tail();
 }
 
 bool fft_plan(const rse_codec* c, const ReconPlan& plan) {
@@ -1218,23 +1210,34 @@ bool fft_plan(const rse_codec* c, const ReconPlan& plan) {
                           plan.rows.c.data());
 }
 
-int reconstruct_impl(const rse_codec* c, void* const* shards, const size_t* lens,
-                     const uint8_t* present, size_t n, bool data_only, hipStream_t s) {
-  if (!c) return RSE_ERR_INVALID_ARGUMENT;
+// n_stripes stripes, `stride` bytes apart, that share one erasure pattern
+// (`shards`: stripe 0's): planned once on the host (with the LRU), then coded
+// by the pattern's own kernel if it has one, else the bit-sliced syndrome
+// kernel, the table kernels for the rest.
+int reconstruct_stripes(const rse_codec* c, void* const* shards, const size_t* lens,
+                        const uint8_t* present, size_t n, bool data_only, uint64_t stride,
+                        size_t n_stripes, hipStream_t s) {
   ReconPlan plan;
   int rc = plan_reconstruct(c, shards, lens, present, n, data_only, plan, true);
   if (rc || plan.nothing_to_do || plan.rows.n_out == 0) return rc;
-  if (plan.fft16) return run_fft16_plan(c, plan, 0, 1, s);
-  if (fft_plan(c, plan)) return run_plan_tail(c, plan, 0, 0, 1, s);
-  if (pattern_kernel(c, plan, plan.len * c->esize())) {
+  const size_t len = plan.len * c->esize();
+  if (plan.fft16) return run_fft16_plan(c, plan, stride, n_stripes, s);
+  if (fft_plan(c, plan)) return run_plan_tail(c, plan, 0, stride, n_stripes, s);
+  if (pattern_kernel(c, plan, len, len * n_stripes)) {
     ++g_pattern_launches;
-    return run_plan_tail(c, plan, 0, 0, 1, s);  // launch_code finds the pattern's kernel
+    return run_plan_tail(c, plan, 0, stride, n_stripes, s);  // launch_code finds the pattern's kernel
   }
   size_t done = 0;
   rc = bitslice_reconstruct(c, reinterpret_cast<const uint8_t* const*>(shards), present, data_only,
-                            plan.len * c->esize(), 0, 1, s, &done);
+                            len, stride, n_stripes, s, &done);
   if (rc) return rc;
-  return run_plan_tail(c, plan, done, 0, 1, s);
+  return run_plan_tail(c, plan, done, stride, n_stripes, s);
+}
+
+int reconstruct_impl(const rse_codec* c, void* const* shards, const size_t* lens,
+                     const uint8_t* present, size_t n, bool data_only, hipStream_t s) {
+  if (!c) return RSE_ERR_INVALID_ARGUMENT;
+  return reconstruct_stripes(c, shards, lens, present, n, data_only, 0, 1, s);
 }
 
 int host_code(int field, const Rows& rows, const void* const* in, void* const* out, size_t len_bytes,
@@ -1243,9 +1246,7 @@ int host_code(int field, const Rows& rows, const void* const* in, void* const* o
 // host: the shards are in host memory (rse_encode_sep_host): same validation,
 // then the host pipeline instead of device launches.
 // n_stripes flat stripes that share one erasure pattern (reconstruct, or
-// reconstruct_data: the wasm ABI, wasm/src/lib.rs:57-73): planned once on the
-// host (with the LRU), then coded by the pattern's own kernel if it has one,
-// else the bit-sliced syndrome kernel, the table kernels for the rest.
+// reconstruct_data: the wasm ABI, wasm/src/lib.rs:57-73).
 int flat_reconstruct(const rse_codec* c, uint8_t* base, size_t shard_len, size_t n_stripes,
                      const uint8_t* present, bool data_only, hipStream_t s) {
   if (n_stripes == 0) return RSE_OK;
@@ -1253,21 +1254,8 @@ int flat_reconstruct(const rse_codec* c, uint8_t* base, size_t shard_len, size_t
   std::vector<void*> ptrs(c->total);
   std::vector<size_t> lens(c->total, shard_len);
   for (size_t i = 0; i < c->total; ++i) ptrs[i] = base + i * sb;
-  ReconPlan plan;
-  int rc = plan_reconstruct(c, ptrs.data(), lens.data(), present, c->total, data_only, plan, true);
-  if (rc || plan.nothing_to_do || plan.rows.n_out == 0) return rc;
-  const uint64_t stride = (uint64_t)c->total * sb;
-  if (plan.fft16) return run_fft16_plan(c, plan, stride, n_stripes, s);
-  if (fft_plan(c, plan)) return run_plan_tail(c, plan, 0, stride, n_stripes, s);
-  if (pattern_kernel(c, plan, sb, sb * n_stripes)) {
-    ++g_pattern_launches;
-    return run_plan_tail(c, plan, 0, stride, n_stripes, s);
-  }
-  size_t done = 0;
-  rc = bitslice_reconstruct(c, reinterpret_cast<const uint8_t* const*>(ptrs.data()), present,
-                            data_only, sb, stride, n_stripes, s, &done);
-  if (rc) return rc;
-  return run_plan_tail(c, plan, done, stride, n_stripes, s);
+  return reconstruct_stripes(c, ptrs.data(), lens.data(), present, c->total, data_only,
+                             (uint64_t)c->total * sb, n_stripes, s);
 }
 
 int encode_sep_impl(const rse_codec* c, const void* const* data, const size_t* data_lens,
@@ -1735,11 +1723,19 @@ int host_code(int field, const Rows& rows, const void* const* in, void* const* o
                        len_bytes, s, nullptr, &hc);
 }
 
-// Flat host stripes: shard i of stripe s at base + (s * total + i) * sb.
-std::vector<void*> flat_ptrs(const rse_codec* c, void* base, size_t sb, size_t n_stripes) {
-  std::vector<void*> ptrs(n_stripes * c->total);
+// Flat host stripes: shard i of stripe s at base + (s * total + i) * sb, its
+// presence flag (`present` null: the operation takes none) at
+// present[s * total + i].  The list points into `ptrs`, which it fills.
+std::vector<HostStripe> flat_host_stripes(const rse_codec* c, void* base, size_t sb,
+                                          size_t n_stripes, const uint8_t* present,
+                                          std::vector<void*>& ptrs) {
+  const size_t T = c->total;
+  ptrs.resize(n_stripes * T);
   for (size_t i = 0; i < ptrs.size(); ++i) ptrs[i] = static_cast<uint8_t*>(base) + i * sb;
-  return ptrs;
+  std::vector<HostStripe> list(n_stripes);
+  for (size_t s = 0; s < n_stripes; ++s)
+    list[s] = HostStripe{&ptrs[s * T], nullptr, present ? present + s * T : nullptr, true};
+  return list;
 }
 
 // Makes `dev` current for a scope (dev < 0: no change) and restores the
@@ -2093,6 +2089,39 @@ int run_now(const rse_codec* c, const Rows& rows, const uint8_t* const* in, uint
   return RSE_OK;
 }
 
+// What rse_locate_flat and rse_correct_flat (`what`) do around their kernels,
+// after their own null checks.  Validation first: it touches no device, so the
+// stream's device is made current only after it.  Then the codec's plan there
+// (copied to the device once, on the first call), the per-stripe accumulators
+// in a stream-ordered workspace, launch(args, stream), and the workspace's
+// free.  No host synchronisation.
+template <class Launch>
+int locate_pass(const rse_codec* c, const void* stripes, size_t shard_len, size_t n_stripes,
+                rse_stream_t stream, const char* what, const Launch& launch) {
+  if (!rse::locate_in_scope(c->field, c->k, c->p)) return RSE_ERR_INVALID_ARGUMENT;
+  if (shard_len == 0) return RSE_EMPTY_SHARD;
+  if (n_stripes == 0) return RSE_OK;
+  RSE_ON_STREAM(stream);
+  hipStream_t st = (hipStream_t)stream;
+  int dev = 0;
+  RSE_HIP(hipGetDevice(&dev));
+  rse::LocateArgs a{};
+  RSE_HIP(locate_plan_consts(c, dev, &a.consts));
+  RSE_HIP(hipMallocAsync(reinterpret_cast<void**>(&a.acc),
+                         n_stripes * rse::kLocAccWords * sizeof(uint32_t), st));
+  a.base = static_cast<const uint8_t*>(stripes);
+  a.shard_bytes = shard_len;
+  a.n_stripes = n_stripes;
+  a.k = (uint32_t)c->k;
+  a.p = (uint32_t)c->p;
+  const hipError_t e = launch(a, st);
+  const hipError_t f = hipFreeAsync(a.acc, st);
+  if (e != hipSuccess) return dev_fail(e);
+  if (f != hipSuccess) return dev_fail(f);
+  rse::note_kernel("%s gf8 %zu+%zu", what, c->k, c->p);
+  return RSE_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2195,76 +2224,30 @@ int rse_verify_flat(const rse_codec* c, const void* stripes, size_t shard_len, s
 }
 
 // Which shards of every stripe are wrong (rse_locate.hip): the locating pass
-// into per-stripe accumulators in a stream-ordered workspace, then the pass
-// that writes present / status.  Validation first; no host synchronisation
-// (the codec's plan is copied to the device once, on the first call there).
+// into per-stripe accumulators, then the pass that writes present / status
+// (locate_pass).
 int rse_locate_flat(const rse_codec* c, const void* stripes, size_t shard_len, size_t n_stripes,
                     uint8_t* present, uint8_t* status, rse_stream_t stream) {
   if (!c || !stripes || !present || !status) return RSE_ERR_INVALID_ARGUMENT;
-  if (!rse::locate_in_scope(c->field, c->k, c->p)) return RSE_ERR_INVALID_ARGUMENT;
-  if (shard_len == 0) return RSE_EMPTY_SHARD;
-  if (n_stripes == 0) return RSE_OK;
-  RSE_ON_STREAM(stream);
-  hipStream_t st = (hipStream_t)stream;
-  int dev = 0;
-  RSE_HIP(hipGetDevice(&dev));
-  const uint8_t* consts = nullptr;
-  RSE_HIP(locate_plan_consts(c, dev, &consts));
-  uint32_t* acc = nullptr;
-  RSE_HIP(hipMallocAsync(reinterpret_cast<void**>(&acc),
-                         n_stripes * rse::kLocAccWords * sizeof(uint32_t), st));
-  rse::LocateArgs a{};
-  a.base = static_cast<const uint8_t*>(stripes);
-  a.shard_bytes = shard_len;
-  a.n_stripes = n_stripes;
-  a.k = (uint32_t)c->k;
-  a.p = (uint32_t)c->p;
-  a.consts = consts;
-  a.acc = acc;
-  const hipError_t e = rse::launch_locate(a, present, status, st);
-  const hipError_t f = hipFreeAsync(acc, st);
-  if (e != hipSuccess) return dev_fail(e);
-  if (f != hipSuccess) return dev_fail(f);
-  rse::note_kernel("locate gf8 %zu+%zu", c->k, c->p);
-  return RSE_OK;
+  return locate_pass(c, stripes, shard_len, n_stripes, stream, "locate",
+                     [&](const rse::LocateArgs& a, hipStream_t st) {
+                       return rse::launch_locate(a, present, status, st);
+                     });
 }
 
 // Repairs the wrong bytes of every stripe where they lie (rse_correct.hip):
-// the repairing pass, which also fills per-stripe accumulators in a
-// stream-ordered workspace, then the pass that writes status / changed /
-// counts.  Validation first, in rse_locate_flat's order; no host
-// synchronisation (the plan is the one rse_locate_flat copies, once per device).
+// the repairing pass, which also fills per-stripe accumulators, then the pass
+// that writes status / changed / counts (locate_pass: rse_locate_flat's
+// validation order, and the plan it copies, once per device).
 int rse_correct_flat(const rse_codec* c, void* stripes, size_t shard_len, size_t n_stripes,
                      const uint8_t* present, uint8_t* status, uint8_t* changed, uint32_t* counts,
                      rse_stream_t stream) {
   if (!c || !stripes || !status) return RSE_ERR_INVALID_ARGUMENT;
-  if (!rse::locate_in_scope(c->field, c->k, c->p)) return RSE_ERR_INVALID_ARGUMENT;
-  if (shard_len == 0) return RSE_EMPTY_SHARD;
-  if (n_stripes == 0) return RSE_OK;
-  RSE_ON_STREAM(stream);
-  hipStream_t st = (hipStream_t)stream;
-  int dev = 0;
-  RSE_HIP(hipGetDevice(&dev));
-  const uint8_t* consts = nullptr;
-  RSE_HIP(locate_plan_consts(c, dev, &consts));
-  uint32_t* acc = nullptr;
-  RSE_HIP(hipMallocAsync(reinterpret_cast<void**>(&acc),
-                         n_stripes * rse::kLocAccWords * sizeof(uint32_t), st));
-  rse::CorrectArgs a{};
-  a.loc.base = static_cast<const uint8_t*>(stripes);
-  a.loc.shard_bytes = shard_len;
-  a.loc.n_stripes = n_stripes;
-  a.loc.k = (uint32_t)c->k;
-  a.loc.p = (uint32_t)c->p;
-  a.loc.consts = consts;
-  a.loc.acc = acc;
-  a.present = present;
-  const hipError_t e = rse::launch_correct(a, status, changed, counts, st);
-  const hipError_t f = hipFreeAsync(acc, st);
-  if (e != hipSuccess) return dev_fail(e);
-  if (f != hipSuccess) return dev_fail(f);
-  rse::note_kernel("correct gf8 %zu+%zu", c->k, c->p);
-  return RSE_OK;
+  return locate_pass(c, stripes, shard_len, n_stripes, stream, "correct",
+                     [&](const rse::LocateArgs& a, hipStream_t st) {
+                       return rse::launch_correct(rse::CorrectArgs{a, present}, status, changed,
+                                                  counts, st);
+                     });
 }
 
 int rse_reconstruct_data_flat(const rse_codec* c, void* stripes, size_t shard_len,
@@ -2577,12 +2560,7 @@ int rse_code_shards(int field, const uint8_t* rows, size_t n_out, size_t n_in,
     return RSE_ERR_INVALID_ARGUMENT;
   if (n_out == 0 || n_in == 0 || len == 0) return RSE_OK;
   const size_t es = field == RSE_FIELD_GF16 ? 2 : 1;
-  Rows r;
-  r.n_out = n_out;
-  r.n_in = n_in;
-  r.c.resize(n_out * n_in);
-  for (size_t i = 0; i < n_out * n_in; ++i)
-    r.c[i] = es == 2 ? (uint16_t)((rows[2 * i] << 8) | rows[2 * i + 1]) : rows[i];
+  const Rows r = rows_from_bytes(field, rows, n_out, n_in);
   Job j{field, &r, reinterpret_cast<const uint8_t* const*>(inputs),
         reinterpret_cast<uint8_t* const*>(outputs), nullptr, len * es, rse::kStore,
         accumulate != 0, nullptr, 0, 1};
@@ -2602,12 +2580,7 @@ int rse_code_shards_host(int field, const uint8_t* rows, size_t n_out, size_t n_
     return RSE_ERR_INVALID_ARGUMENT;
   if (n_out == 0 || n_in == 0 || len == 0) return RSE_OK;
   const size_t es = field == RSE_FIELD_GF16 ? 2 : 1;
-  Rows r;
-  r.n_out = n_out;
-  r.n_in = n_in;
-  r.c.resize(n_out * n_in);
-  for (size_t i = 0; i < n_out * n_in; ++i)
-    r.c[i] = es == 2 ? (uint16_t)((rows[2 * i] << 8) | rows[2 * i + 1]) : rows[i];
+  const Rows r = rows_from_bytes(field, rows, n_out, n_in);
   return host_code(field, r, inputs, outputs, len * es, accumulate != 0, (hipStream_t)stream);
 }
 
@@ -2718,9 +2691,8 @@ int rse_encode_host_flat(const rse_codec* c, void* stripes, size_t shard_len, si
   if (n_stripes == 0) return RSE_OK;
   if (shard_len == 0) return RSE_EMPTY_SHARD;
   const size_t sb = shard_len * c->esize();
-  const std::vector<void*> ptrs = flat_ptrs(c, stripes, sb, n_stripes);
-  std::vector<HostStripe> list(n_stripes);
-  for (size_t s = 0; s < n_stripes; ++s) list[s] = HostStripe{&ptrs[s * c->total], nullptr, nullptr, true};
+  std::vector<void*> ptrs;
+  const auto list = flat_host_stripes(c, stripes, sb, n_stripes, nullptr, ptrs);
   return host_pipeline(c, HostOp::kEncode, list, sb, (hipStream_t)stream, nullptr);
 }
 
@@ -2758,9 +2730,9 @@ int rse_verify_host_flat(const rse_codec* c, const void* stripes, size_t shard_l
   if (shard_len == 0) return RSE_EMPTY_SHARD;
   if (n_stripes == 0) return RSE_OK;
   const size_t sb = shard_len * c->esize();
-  const std::vector<void*> ptrs = flat_ptrs(c, const_cast<void*>(stripes), sb, n_stripes);
-  std::vector<HostStripe> list(n_stripes);
-  for (size_t s = 0; s < n_stripes; ++s) list[s] = HostStripe{&ptrs[s * c->total], nullptr, nullptr, true};
+  std::vector<void*> ptrs;
+  const auto list =
+      flat_host_stripes(c, const_cast<void*>(stripes), sb, n_stripes, nullptr, ptrs);
   std::vector<int> res(n_stripes, 0);
   const int rc = host_pipeline(c, HostOp::kVerify, list, sb, (hipStream_t)stream, res.data());
   if (rc == RSE_OK)
@@ -2806,10 +2778,8 @@ int rse_reconstruct_host_batch(const rse_codec* c, void* stripes, size_t shard_l
     if (np < k) return RSE_TOO_FEW_SHARDS_PRESENT;
   }
   const size_t sb = shard_len * c->esize();
-  const std::vector<void*> ptrs = flat_ptrs(c, stripes, sb, n_stripes);
-  std::vector<HostStripe> list(n_stripes);
-  for (size_t s = 0; s < n_stripes; ++s)
-    list[s] = HostStripe{&ptrs[s * T], nullptr, present + s * T, true};
+  std::vector<void*> ptrs;
+  const auto list = flat_host_stripes(c, stripes, sb, n_stripes, present, ptrs);
   return host_pipeline(c, data_only ? HostOp::kReconData : HostOp::kRecon, list, sb,
                        (hipStream_t)stream, nullptr);
 }

@@ -176,44 +176,22 @@ __global__ __launch_bounds__(256) void correct_finalize_kernel(const uint32_t* _
   }
 }
 
-template <int NO>
-void launch_correct_no(const CorrectArgs& a, dim3 grid, hipStream_t stream) {
-  constexpr uint32_t KCH = loc_tabs<NO>() / NO;
-  if constexpr (KCH < 254u) {  // k <= 254: only NO = 16 can need more than one chunk
-    if (a.loc.k > KCH) {
-      hipLaunchKernelGGL((correct_kernel<NO, true>), grid, dim3(kLocBlock), 0, stream, a);
-      return;
-    }
-  }
-  hipLaunchKernelGGL((correct_kernel<NO, false>), grid, dim3(kLocBlock), 0, stream, a);
-}
-
 }  // namespace
 
 hipError_t launch_correct(const CorrectArgs& args, uint8_t* status, uint8_t* changed,
                           uint32_t* counts, hipStream_t stream) {
   static_assert(kCorAccBad == kCorAccStored + 2 && kCorAccSkipped < kLocAccWords, "accumulator");
   CorrectArgs a = args;
-  const uint32_t n = a.loc.k + a.loc.p;
-  if (!locate_in_scope(8, a.loc.k, a.loc.p) || a.loc.shard_bytes == 0 || a.loc.n_stripes == 0)
-    return hipErrorInvalidValue;
-  hipError_t e =
-      hipMemsetAsync(a.loc.acc, 0, a.loc.n_stripes * kLocAccWords * sizeof(uint32_t), stream);
-  if (e != hipSuccess) return e;
-  const dim3 grid = loc_grid(a.loc);
-  if (a.loc.p <= 4)
-    launch_correct_no<4>(a, grid, stream);
-  else if (a.loc.p <= 8)
-    launch_correct_no<8>(a, grid, stream);
-  else
-    launch_correct_no<16>(a, grid, stream);
-  e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  const uint64_t total = a.loc.n_stripes * n;
-  const uint64_t fb = (total + 255u) / 256u;
-  hipLaunchKernelGGL(correct_finalize_kernel, dim3((uint32_t)(fb < 65536u ? fb : 65536u)),
-                     dim3(256), 0, stream, a.loc.acc, a.loc.n_stripes, n, status, changed, counts);
-  return hipGetLastError();
+  return loc_launch(
+      a.loc, stream,
+      [&](auto no, auto multi, dim3 grid) {
+        hipLaunchKernelGGL((correct_kernel<decltype(no)::value, decltype(multi)::value>), grid,
+                           dim3(kLocBlock), 0, stream, a);
+      },
+      [&](dim3 blocks) {
+        hipLaunchKernelGGL(correct_finalize_kernel, blocks, dim3(256), 0, stream, a.loc.acc,
+                           a.loc.n_stripes, a.loc.k + a.loc.p, status, changed, counts);
+      });
 }
 
 }  // namespace rse

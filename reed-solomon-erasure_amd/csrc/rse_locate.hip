@@ -116,42 +116,21 @@ __global__ __launch_bounds__(256) void locate_finalize_kernel(const uint32_t* __
   }
 }
 
-template <int NO>
-void launch_locate_no(const LocateArgs& a, dim3 grid, hipStream_t stream) {
-  constexpr uint32_t KCH = loc_tabs<NO>() / NO;
-  if constexpr (KCH < 254u) {  // k <= 254: only NO = 16 can need more than one chunk
-    if (a.k > KCH) {
-      hipLaunchKernelGGL((locate_kernel<NO, true>), grid, dim3(kLocBlock), 0, stream, a);
-      return;
-    }
-  }
-  hipLaunchKernelGGL((locate_kernel<NO, false>), grid, dim3(kLocBlock), 0, stream, a);
-}
-
 }  // namespace
 
 hipError_t launch_locate(const LocateArgs& args, uint8_t* present, uint8_t* status,
                          hipStream_t stream) {
   LocateArgs a = args;
-  const uint32_t n = a.k + a.p;
-  if (!locate_in_scope(8, a.k, a.p) || a.shard_bytes == 0 || a.n_stripes == 0)
-    return hipErrorInvalidValue;
-  hipError_t e = hipMemsetAsync(a.acc, 0, a.n_stripes * kLocAccWords * sizeof(uint32_t), stream);
-  if (e != hipSuccess) return e;
-  const dim3 grid = loc_grid(a);
-  if (a.p <= 4)
-    launch_locate_no<4>(a, grid, stream);
-  else if (a.p <= 8)
-    launch_locate_no<8>(a, grid, stream);
-  else
-    launch_locate_no<16>(a, grid, stream);
-  e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  const uint64_t total = a.n_stripes * n;
-  const uint64_t fb = (total + 255u) / 256u;
-  hipLaunchKernelGGL(locate_finalize_kernel, dim3((uint32_t)(fb < 65536u ? fb : 65536u)),
-                     dim3(256), 0, stream, a.acc, a.n_stripes, n, a.p, present, status);
-  return hipGetLastError();
+  return loc_launch(
+      a, stream,
+      [&](auto no, auto multi, dim3 grid) {
+        hipLaunchKernelGGL((locate_kernel<decltype(no)::value, decltype(multi)::value>), grid,
+                           dim3(kLocBlock), 0, stream, a);
+      },
+      [&](dim3 blocks) {
+        hipLaunchKernelGGL(locate_finalize_kernel, blocks, dim3(256), 0, stream, a.acc,
+                           a.n_stripes, a.k + a.p, a.p, present, status);
+      });
 }
 
 }  // namespace rse

@@ -2,9 +2,11 @@
 // (rse_locate.hip) and rse_correct_flat (rse_correct.hip) share: one unit of a
 // workgroup's sweep forms d = P data ^ parity per byte column with the
 // arithmetic of the table check (rse_kernels.hip gf8_span in kCheck mode) and
-// hands the lanes with a nonzero d to the caller's slow path.  Device code
-// only; included by those two translation units.
+// hands the lanes with a nonzero d to the caller's slow path.  Then the launch
+// sequence the two share (loc_launch).  Included by those two translation units.
 #pragma once
+
+#include <type_traits>
 
 #include "rse_device.hpp"
 #include "rse_locate.hpp"
@@ -171,6 +173,43 @@ inline dim3 loc_grid(LocateArgs& a) {
   if (gx < 1) gx = 1;
   if (gx > units) gx = units;
   return dim3((uint32_t)gx, gy);
+}
+
+// The launch sequence of both entries: the accumulators zeroed, the sweep
+// kernel, the finalize kernel.  sweep(NO, MULTI, grid) launches the caller's
+// sweep kernel for these two integral constants; finalize(blocks) launches its
+// finalize kernel, one thread per (stripe, shard) up to 65536 blocks.  Sets
+// a.n_vec (loc_grid), which the sweep kernel reads.
+template <class Sweep, class Finalize>
+hipError_t loc_launch(LocateArgs& a, hipStream_t stream, const Sweep& sweep,
+                      const Finalize& finalize) {
+  if (!locate_in_scope(8, a.k, a.p) || a.shard_bytes == 0 || a.n_stripes == 0)
+    return hipErrorInvalidValue;
+  hipError_t e = hipMemsetAsync(a.acc, 0, a.n_stripes * kLocAccWords * sizeof(uint32_t), stream);
+  if (e != hipSuccess) return e;
+  const dim3 grid = loc_grid(a);
+  const auto with_no = [&](auto no) {
+    constexpr int NO = decltype(no)::value;
+    constexpr uint32_t KCH = loc_tabs<NO>() / NO;
+    if constexpr (KCH < 254u) {  // k <= 254: only NO = 16 can need more than one chunk
+      if (a.k > KCH) {
+        sweep(no, std::true_type{}, grid);
+        return;
+      }
+    }
+    sweep(no, std::false_type{}, grid);
+  };
+  if (a.p <= 4)
+    with_no(std::integral_constant<int, 4>{});
+  else if (a.p <= 8)
+    with_no(std::integral_constant<int, 8>{});
+  else
+    with_no(std::integral_constant<int, 16>{});
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  const uint64_t fb = (a.n_stripes * (a.k + a.p) + 255u) / 256u;
+  finalize(dim3((uint32_t)(fb < 65536u ? fb : 65536u)));
+  return hipGetLastError();
 }
 
 }  // namespace locate_core
