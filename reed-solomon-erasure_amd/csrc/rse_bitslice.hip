@@ -18,6 +18,7 @@
 #include <atomic>
 #include "rse_bitslice_core.hpp"
 #include "rse_bitslice_ticket.hpp"
+#include "rse_options.hpp"
 
 namespace rse {
 namespace {
@@ -606,7 +607,7 @@ hipError_t launch_bitslice(int field, const CodeArgs& a, bool nt, int64_t grid,
   constexpr uint64_t kV16 = kBsChunk / 16, kV4 = 4096 / 16;  // vectors per chunk
   // shards of exactly 1 or 2 KiB: 4 or 2 stripes per 4 KiB chunk (SUB)
   const bool subm = (a.len == 1024u || a.len == 2048u) && a.n_vec * 16u == a.len &&
-                    get_option(33) != 0;
+                    get_option(RSE_OPT_SUB_CHUNKS) != 0;
   // accumulate: store mode on a wide codec's block kernels (kJitBlock) only
   if ((a.n_vec < kV4 && !subm) || (a.accumulate && a.mode != kStore)) return hipSuccess;
   // the kernels for these coefficients: compiled in, or specialised at run time
@@ -625,7 +626,7 @@ hipError_t launch_bitslice(int field, const CodeArgs& a, bool nt, int64_t grid,
       for (uint32_t i = 0; i < sh.k && same; ++i) same = a.coef[o][i] == sh.m[o * sh.k + i];
     if (!same) break;
     // RSE_OPT_KERNEL_VARIANT picks a bit-sliced variant too (-1: default)
-    const int64_t vopt = get_option(4);
+    const int64_t vopt = get_option(RSE_OPT_KERNEL_VARIANT);
     const int vdef = field == 16 ? kBsDefaultVariant16 : kBsDefaultVariant8;
     int v = (vopt >= 0 && vopt < kBsVariants) ? (int)vopt : vdef;
     shape = &sh;
@@ -654,7 +655,8 @@ hipError_t launch_bitslice(int field, const CodeArgs& a, bool nt, int64_t grid,
     j4 = a.accumulate ? jf.enc4_acc : jf.enc4;
     js = a.accumulate ? nullptr : jf.sub[a.len == 2048u];
     if (!j16) return hipSuccess;
-    if (a.mode != kStore && !a.accumulate && nt && jf.chk && get_option(4) < 0) {
+    if (a.mode != kStore && !a.accumulate && nt && jf.chk &&
+        get_option(RSE_OPT_KERNEL_VARIANT) < 0) {
       j16 = jf.chk;  // the check kernel, which can signal the call's completion
       chk = true;
     }
@@ -714,8 +716,8 @@ hipError_t launch_bitslice(int field, const CodeArgs& a, bool nt, int64_t grid,
   // call's 40.9 us).  The counters are 32-bit.
   BsTicketFn ftk = nullptr;
   if (compiled && cps16 && cps16 * a.n_stripes < 0x40000000u) {
-    if (tk_slot < 0 && kBsTicketDefault >= 10 && get_option(4) < 0 && field == 8 && nt &&
-        a.mode == kStore) {
+    if (tk_slot < 0 && kBsTicketDefault >= 10 && get_option(RSE_OPT_KERNEL_VARIANT) < 0 &&
+        field == 8 && nt && a.mode == kStore) {
       // rounds of the workgroups the ticket kernel itself holds (its occupancy), as its grid
       const int d = kBsTicketDefault - 10;
       if (cps16 * a.n_stripes >
@@ -751,7 +753,7 @@ hipError_t launch_bitslice(int field, const CodeArgs& a, bool nt, int64_t grid,
       // partial last round (profiles/ticket/grid_sweep.log, timeline.log).
       const uint64_t total = cps16 * a.n_stripes;
       uint64_t gx = ticket_resident(ftk, (int)(shape - kBsShapes) * 2 + tk_slot) *
-                    (uint64_t)get_option(55);
+                    (uint64_t)get_option(RSE_OPT_TICKET_GRID);
       if (gx > total) gx = total;
       if (grid > 0) gx = (uint64_t)grid < 0x20000000u ? (uint64_t)grid : 0x20000000u;
       // The counter words live for this launch only: allocated, zeroed and
@@ -802,7 +804,7 @@ hipError_t launch_bitslice(int field, const CodeArgs& a, bool nt, int64_t grid,
 // at 8 lost, 256 stripes: 4.96 TB/s against 4.73 for the depth-2 pair and
 // 4.79 for round 3's, profiles/r04/s8/r8ab.log), GF(2^16) the depth-2 pair.
 int64_t pair_option(int field) {
-  const int64_t o = get_option(28);
+  const int64_t o = get_option(RSE_OPT_RECON_PAIRS);
   return o == 8 ? (field == 8 ? 2 : 1) : o;
 }
 int pair_groups(int field) {
@@ -815,7 +817,7 @@ int pair_groups(int field) {
 // shared-pattern and the per-stripe (batch) paths alike; it then selects the
 // deep Horner kernel in place of the mode's own.
 int recon_depth(int mix) {
-  return mix >= kReconMixHorner ? (int)get_option(27) : 1;
+  return mix >= kReconMixHorner ? (int)get_option(RSE_OPT_RECON_DEPTH) : 1;
 }
 
 // index into BsShape::rec_pair / rec_desc_pair: option 28 = 3 the prefetching
@@ -838,21 +840,21 @@ int pair_slot(int field) {
 // RSE_OPT_RECON_W4_MIN coefficients (default 64), and always for GF(2^16)
 // proper, whose table kernels are 2 x 2 blocks of GF(2^8) ones.
 bool recon4_pays(int field, uint32_t k, uint32_t n_out) {
-  return field == 16 || (int64_t)k * n_out >= get_option(37);
+  return field == 16 || (int64_t)k * n_out >= get_option(RSE_OPT_RECON_W4_MIN);
 }
 
 hipError_t launch_bitslice_recon(int field, uint32_t k, uint32_t p, const uint16_t* parity_rows,
                                  const BsReconArgs& a, uint64_t n_vec, hipStream_t stream,
                                  uint64_t* done) {
   *done = 0;
-  if (!get_option(5) || n_vec < 4096u / 16 || a.n_out == 0 || a.n_out > (uint32_t)kMaxOut ||
-      (a.present == 0 && a.synd == 0))
+  if (!get_option(RSE_OPT_BITSLICE) || n_vec < 4096u / 16 || a.n_out == 0 ||
+      a.n_out > (uint32_t)kMaxOut || (a.present == 0 && a.synd == 0))
     return hipSuccess;
   // whole 16 KiB chunks, then whole 4 KiB chunks of the rest (one per wave)
   const uint64_t cps = n_vec / (kBsChunk / 16);
   const uint64_t cps4 = (n_vec * 16u - cps * kBsChunk) / 4096u, base4 = cps * kBsChunk;
   const uint64_t total = cps * a.n_stripes;
-  const int64_t grid = get_option(2);
+  const int64_t grid = get_option(RSE_OPT_GRID_X);
   // tools/tune.py --op reconstruct --patterns 0 sweeps: GF(2^8) 10+4 x 16 MiB at
   // 32768 workgroups against 8192, 2 lost 5.83 against 5.72 TB/s, 4 lost 5.53
   // against 5.27 (profiles/r03/s17/); GF(2^16) 8192
@@ -875,7 +877,7 @@ hipError_t launch_bitslice_recon(int field, uint32_t k, uint32_t p, const uint16
     for (int q = 0; q < 4 && slot < 0; ++q)
       if (sh.rec[0][q] && (1u << q) >= need) slot = q;
     if (slot < 0) return hipSuccess;
-    const int mix = (int)get_option(17);
+    const int mix = (int)get_option(RSE_OPT_RECON_MIX);
     const int depth = recon_depth(mix);
     static const char* const kMixName[4] = {"mix-tables", "mix-chain", "mix-horner", "mix-horner4"};
     if (cps) {
@@ -952,7 +954,7 @@ hipError_t launch_bitslice_recon_batch(int field, uint32_t k, uint32_t p,
                                        uint32_t n_stripes, uint32_t need, uint32_t e_cap,
                                        BsReconArgs* d_descs, hipStream_t stream, uint64_t* done) {
   *done = 0;
-  if (!get_option(5) || shard_bytes < 4096 || k == 0 || k > (uint32_t)kMaxIn ||
+  if (!get_option(RSE_OPT_BITSLICE) || shard_bytes < 4096 || k == 0 || k > (uint32_t)kMaxIn ||
       p > (uint32_t)kMaxOut || need == 0 || n_stripes == 0 || e_cap > (uint32_t)kMaxOut)
     return hipSuccess;  // (e_cap 0: only parity lost -- rebuilt from the sigma rows)
   BsDescFn sfn = nullptr;
@@ -964,7 +966,7 @@ hipError_t launch_bitslice_recon_batch(int field, uint32_t k, uint32_t p,
     compiled = true;
     for (uint32_t i = 0; i < k * p; ++i)
       if (parity_rows[i] != sh.m[i]) return hipSuccess;
-    const int depth = recon_depth((int)get_option(17));
+    const int depth = recon_depth((int)get_option(RSE_OPT_RECON_MIX));
     for (int q = 0; q < 4 && !sfn; ++q)
       if (sh.rec_desc[q] && (1u << q) >= need) {
         sfn = depth > 1 ? sh.rec_desc_deep[depth > 2 ? 1 : 0][q] : sh.rec_desc[q];
@@ -999,7 +1001,7 @@ hipError_t launch_bitslice_recon_batch(int field, uint32_t k, uint32_t p,
                      data_only, base, shard_bytes, n_stripes, e_cap, d_descs);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  const int64_t grid = get_option(2);
+  const int64_t grid = get_option(RSE_OPT_GRID_X);
   auto grid_for = [&](uint64_t steps) {
     uint64_t gx = grid > 0 ? (uint64_t)grid : pairs ? 32768u * (2 / pair_groups(field)) : 8192u;
     if (gx > steps) gx = steps;

@@ -26,8 +26,7 @@
 #include <string>
 #include <vector>
 
-#include "../../include/rse_hip.h"
-#include "../../include/rse_hip_tune.h"
+#include "rse_options.hpp"
 #include "rse_dispatch.hpp"
 #include "rse_fft.hpp"
 #include "rse_fft16.hpp"
@@ -385,7 +384,7 @@ int run_job(const Job& j, hipStream_t s) {
     // want_bitslice): launch them block by block, 8 outputs at a time
     size_t step = kMaxOut;
     if ((n_in > (size_t)kMaxIn || n_out > rse::kJitMaxOut) && j.len_bytes >= 4096 &&
-        rse::get_option(5) != 0 &&
+        rse::get_option(RSE_OPT_BITSLICE) != 0 &&
         rse::jit_blocks_status(j.field, (uint32_t)n_in, (uint32_t)n_out, j.rows->c.data(),
                                false) == 2)
       step = rse::kJitMaxOut;
@@ -703,7 +702,7 @@ int run_check(Job j, hipStream_t s, int* ok) {
   j.mismatch = lease->wd;
   // RSE_OPT_SPIN_WAIT: offer the kernel the completion word; launch_bitslice
   // arms it when one compiled check-kernel launch is the whole verify
-  if (!j.per_stripe && rse::get_option(31)) {
+  if (!j.per_stripe && rse::get_option(RSE_OPT_SPIN_WAIT)) {
     if (!lease->count) {
       RSE_HIP(hipMalloc(reinterpret_cast<void**>(&lease->count), sizeof(uint32_t)));
       RSE_HIP(hipMemset(lease->count, 0, sizeof(uint32_t)));
@@ -733,7 +732,7 @@ int run_check(Job j, hipStream_t s, int* ok) {
       se = hipMemsetAsync(lease->count, 0, sizeof(uint32_t), s);
       if (se == hipSuccess) se = hipStreamSynchronize(s);
     }
-  } else if (rse::get_option(30)) {
+  } else if (rse::get_option(RSE_OPT_SYNC_EVENT)) {
     if (!lease->done) se = hipEventCreateWithFlags(&lease->done, hipEventDisableTiming);
     if (se == hipSuccess) se = hipEventRecord(lease->done, s);
     if (se == hipSuccess) se = hipEventSynchronize(lease->done);
@@ -2784,23 +2783,8 @@ int rse_reconstruct_host_batch(const rse_codec* c, void* stripes, size_t shard_l
                        (hipStream_t)stream, nullptr);
 }
 
-// The keys include/rse_hip.h gives callers; every other settable key is a
-// tuning / A-B switch (include/rse_hip_tune.h), refused unless the process
-// environment has RSE_TUNE=1.
-bool caller_option(int key) {
-  switch (key) {
-    case RSE_OPT_HOST_CHUNK_KIB: case RSE_OPT_HOST_H2D_STREAMS: case RSE_OPT_JIT:
-    case RSE_OPT_JIT_PATTERNS: case RSE_OPT_JIT_DISK_CACHE: case RSE_OPT_JIT_MAX_PATTERNS:
-    case RSE_OPT_JIT_MAX_PATTERN_BLOCKS: case RSE_OPT_DISPATCH: case RSE_OPT_DISPATCH_IDLE_US:
-    case RSE_OPT_DISPATCH_MAX_BYTES: case RSE_OPT_DISPATCH_WORKGROUPS:
-      return true;
-    default:
-      return false;
-  }
-}
-
 int rse_set_option(int key, int64_t value) {
-  if (!caller_option(key)) {
+  if (!rse::caller_may_set_option(key)) {
     const char* t = std::getenv("RSE_TUNE");
     if (!t || std::strcmp(t, "1") != 0) return RSE_ERR_INVALID_ARGUMENT;
   }

@@ -52,6 +52,7 @@
 
 #include "rse_device.hpp"
 #include "rse_dispatch.hpp"
+#include "rse_options.hpp"
 
 namespace rse {
 namespace {
@@ -333,12 +334,12 @@ hipError_t disp_init(Dispatcher& d) {
 // at_least: the workgroups a pending request names (the option may have
 // changed since it was posted).
 hipError_t disp_launch(Dispatcher& d, uint32_t at_least = 1) {
-  const int64_t g = get_option(45);  // RSE_OPT_DISPATCH_WORKGROUPS
+  const int64_t g = get_option(RSE_OPT_DISPATCH_WORKGROUPS);
   d.n_wgs = std::max<uint32_t>(at_least,
                                (uint32_t)(g < 1 ? 1 : g > (int64_t)kMaxDispWgs ? kMaxDispWgs : g));
   for (uint32_t w = 0; w < kMaxDispWgs; ++w)
     reinterpret_cast<volatile uint64_t*>(d.ack)[w * kAckStride] = (uint64_t)d.served;
-  const int64_t idle_us = get_option(40);
+  const int64_t idle_us = get_option(RSE_OPT_DISPATCH_IDLE_US);
   hipLaunchKernelGGL(rse_dispatch_kernel, dim3(d.n_wgs), dim3(kDispThreads), 0, d.st, d.dreq,
                      d.dack, d.served, (uint64_t)(idle_us < 1 ? 1 : idle_us) * 100u);
   const hipError_t e = hipGetLastError();
@@ -386,9 +387,9 @@ void retract(Dispatcher& d) {
 
 bool dispatch_applies(int field, uint32_t n_in, uint32_t n_out, uint64_t len_bytes,
                       const uint8_t* const* in, uint8_t* const* out) {
-  if (!get_option(39) || field != 8 || n_in == 0 || n_out == 0 || n_in > kDispMaxIn ||
+  if (!get_option(RSE_OPT_DISPATCH) || field != 8 || n_in == 0 || n_out == 0 || n_in > kDispMaxIn ||
       n_out > kDispMaxOut || n_in * n_out > kDispMaxCoef || len_bytes == 0 ||
-      len_bytes % 16u != 0 || (int64_t)len_bytes > get_option(41))
+      len_bytes % 16u != 0 || (int64_t)len_bytes > get_option(RSE_OPT_DISPATCH_MAX_BYTES))
     return false;
   const uint32_t n_gran = 1 + n_in + n_out + (n_in * n_out + 11) / 12;
   if (n_gran > (uint32_t)kMaxGranules) return false;
@@ -420,13 +421,15 @@ hipError_t dispatch_run(const uint16_t* rows, uint32_t n_in, uint32_t n_out,
   // many as the running kernel has; outputs per work item: items (vectors x
   // output blocks) for their lanes
   const uint64_t n_vec = len_bytes / 16u;
-  if (!d.running) d.n_wgs = (uint32_t)std::min<int64_t>(std::max<int64_t>(get_option(45), 1),
-                                                          kMaxDispWgs);
+  if (!d.running)
+    d.n_wgs = (uint32_t)std::min<int64_t>(
+        std::max<int64_t>(get_option(RSE_OPT_DISPATCH_WORKGROUPS), 1), kMaxDispWgs);
   // (profiles/r05/s10/latency.log, 8 resident, 10+4: 4 KiB 6.6 us on one
   // workgroup against 7.3 on two; 8 / 16 KiB 8.0 / 8.3 us at one unit per
   // lane against 8.4 / 9.2 at two and 8.9 / 10.6 at four)
   const uint64_t units = n_vec * n_out;
-  const uint64_t per_wg = (uint64_t)std::max<int64_t>(get_option(49), 1) * kDispThreads;
+  const uint64_t per_wg =
+      (uint64_t)std::max<int64_t>(get_option(RSE_OPT_DISPATCH_LANE_UNITS), 1) * kDispThreads;
   const uint32_t n_wg =
       units <= 2u * kDispThreads
           ? 1u  // a request within 2 units per lane of one workgroup stays on it

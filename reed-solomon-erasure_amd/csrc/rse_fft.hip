@@ -59,6 +59,7 @@
 #include "rse_field.hpp"
 #include "rse_fft.hpp"
 #include "rse_fft_sched.hpp"
+#include "rse_options.hpp"
 
 namespace rse {
 namespace {
@@ -409,7 +410,7 @@ hipError_t fft_launch(const FftLaunch& l) {
   if (e == hipSuccess) e = hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev);
   if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, fn, threads, 0);
   if (e != hipSuccess) return e;
-  const int64_t grid_opt = get_option(2);
+  const int64_t grid_opt = get_option(RSE_OPT_GRID_X);
   uint64_t gx = grid_opt > 0 ? (uint64_t)grid_opt : (uint64_t)std::max(per, 1) * (uint64_t)n_cu;
   if (gx > total) gx = total;
   if (gx > 0x7fffffffu) gx = 0x7fffffffu;
@@ -420,7 +421,7 @@ hipError_t fft_launch(const FftLaunch& l) {
 }  // namespace
 
 bool fft_applies(int field, uint32_t k, uint32_t p, const uint16_t* rows) {
-  const int64_t opt = get_option(51);
+  const int64_t opt = get_option(RSE_OPT_FFT);
   if (field != 8 || k != p || !opt) return false;
   const std::vector<uint16_t>* par = nullptr;
   switch (k) {
@@ -443,7 +444,7 @@ hipError_t launch_fft(int field, uint32_t k, uint32_t p, const uint16_t* rows,
   *done = 0;
   if (!fft_applies(field, k, p, rows) || n_stripes == 0) return hipSuccess;
   // 1 KiB shards: two stripes per 2 KiB column; otherwise whole 2 KiB columns
-  const uint32_t sub = len == 1024u && get_option(33) != 0 ? 1024u : 0u;
+  const uint32_t sub = len == 1024u && get_option(RSE_OPT_SUB_CHUNKS) != 0 ? 1024u : 0u;
   const uint64_t cols = len / 2048u;
   if (!sub && cols == 0) return hipSuccess;
   const FftLaunch l{stripe_stride, cols, mismatch, n_stripes, mode, per_stripe ? 1u : 0u, sub,

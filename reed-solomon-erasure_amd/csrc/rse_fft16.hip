@@ -47,6 +47,7 @@
 
 #include "rse_bitslice_core.hpp"
 #include "rse_fft16.hpp"
+#include "rse_options.hpp"
 
 namespace rse {
 namespace {
@@ -316,7 +317,8 @@ hipError_t fft16_twiddles(Fft16Entry* e, const uint32_t** out) {
 }  // namespace
 
 const Fft16Plan* fft16_plan(int field, uint32_t k, uint32_t p) {
-  if (field != 16 || !get_option(54) || !fft16_shape(k, p, nullptr, nullptr)) return nullptr;
+  if (field != 16 || !get_option(RSE_OPT_FFT16) || !fft16_shape(k, p, nullptr, nullptr))
+    return nullptr;
   Fft16Entry* e = fft16_entry(k, p);
   return e ? &e->plan : nullptr;
 }
@@ -379,7 +381,7 @@ hipError_t launch_fft16(const Fft16Plan& pl, const uint8_t* const* in, uint32_t 
     he = hipGetDevice(&dev);
     if (he == hipSuccess) he = hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev);
     if (he == hipSuccess) {
-      const int64_t grid_opt = get_option(2);
+      const int64_t grid_opt = get_option(RSE_OPT_GRID_X);
       uint64_t gx = grid_opt > 0 ? (uint64_t)grid_opt : (uint64_t)std::max(n_cu, 1);
       if (gx > a.total) gx = a.total;
       if (gx > 0x7fffffffu) gx = 0x7fffffffu;

@@ -43,10 +43,10 @@
 #include <utility>
 #include <vector>
 
-#include "../../include/rse_hip.h"
 #include "rse_field.hpp"
 #include "rse_kernels.hpp"
 #include "rse_netgen.hpp"
+#include "rse_options.hpp"
 #include "rse_wideblk.hpp"
 
 extern char** environ;
@@ -115,8 +115,10 @@ std::atomic<int64_t> g_built{0};
 int g_patterns = 0;  // decode-pattern entries (capped: max_patterns)
 // per process: RSE_OPT_JIT_MAX_PATTERNS (default 64) decode-pattern modules,
 // RSE_OPT_JIT_MAX_PATTERN_BLOCKS (64) blocks of wide decode patterns
-int max_patterns() { return (int)std::min<int64_t>(get_option(35), 1 << 30); }
-int max_pattern_blocks() { return (int)std::min<int64_t>(get_option(36), 1 << 30); }
+int max_patterns() { return (int)std::min<int64_t>(get_option(RSE_OPT_JIT_MAX_PATTERNS), 1 << 30); }
+int max_pattern_blocks() {
+  return (int)std::min<int64_t>(get_option(RSE_OPT_JIT_MAX_PATTERN_BLOCKS), 1 << 30);
+}
 int g_blocks = 0;  // wide-codec block entries (capped: kMaxBlocks)
 constexpr int kMaxBlocks = 1024;  // 128+128: 64, GF(2^16) 1000+24: 120
 // blocks of wide decode patterns: a separate budget, so patterns can never
@@ -171,7 +173,8 @@ int recon_ns(uint32_t p, int* ns) {
 void emit_code(std::string& s, const char* name, int field, uint32_t k, uint32_t p,
                const std::vector<uint16_t>& rows, int temps, bool pairs = false) {
   const netgen::Net net = pairs ? netgen::build_pairs(k, p, rows.data(), temps)
-                                : netgen::build(field, k, p, rows.data(), temps, get_option(23) != 0);
+                                : netgen::build(field, k, p, rows.data(), temps,
+                                                get_option(RSE_OPT_JIT_EXACT) != 0);
   s += "\nnamespace rse {\nnamespace {\n";
   s += netgen::emit(net, name, rows.data());
   s += "}  // namespace\n}  // namespace rse\n";
@@ -193,9 +196,9 @@ void emit_code(std::string& s, const char* name, int field, uint32_t k, uint32_t
 // s64.log; 32+32 and 50+20 are not faster at 4, s32.log, s50.log).
 int wide_waves(uint32_t p, int field = 0) {
   uint32_t per = wide_per_wave();
-  if (get_option(18) == 0 && field == 8 && p > 48) per = 4;
+  if (get_option(RSE_OPT_WIDE_SPLIT) == 0 && field == 8 && p > 48) per = 4;
   int w = (int)((p + per - 1) / per);
-  if (get_option(19) != 0 && p >= 4) {
+  if (get_option(RSE_OPT_WIDE_BALANCE) != 0 && p >= 4) {
     int b = 4;
     while (b < w) b *= 2;
     if ((uint32_t)b <= p) w = b;
@@ -208,7 +211,7 @@ int wide_waves(uint32_t p, int field = 0) {
 // spill (GF(2^8) 50+20 in 4 waves: 168 VGPRs and 25 spills at 3, 156 and none
 // at 2 -- which runs 3 waves per SIMD all the same).
 int wide_waves_per_eu(uint32_t) {
-  const int64_t o = get_option(20);  // RSE_OPT_WIDE_OCCUPANCY
+  const int64_t o = get_option(RSE_OPT_WIDE_OCCUPANCY);
   return o ? (int)o : 2;
 }
 void wide_share(uint32_t p, int W_, int w, uint32_t* o0, uint32_t* n) {
@@ -233,26 +236,27 @@ std::string make_source(int field, uint32_t k, uint32_t p, const std::vector<uin
 #ifdef RSE_TUNE_SPLITS
   // timing split (tools/tune.py's build only, WRONG bytes): wide modules
   // without their workgroup barriers, what the per-round synchronisation costs
-  if (kind == kJitWide && get_option(47) == 1) s += "#define __syncthreads() ((void)0)\n";
+  if (kind == kJitWide && get_option(RSE_OPT_TUNE_NOSYNC) == 1)
+    s += "#define __syncthreads() ((void)0)\n";
 #endif
   s += kJitSource;
   // RSE_OPT_SUB_DEPTH > 1: the narrow modules' 1 / 2 KiB-shard kernels with
   // that many inputs in flight per wave (rse_sub_ext.hpp)
-  const int sub_depth = kind != kJitWide && stage == kEnc ? (int)get_option(50) : 1;
+  const int sub_depth = kind != kJitWide && stage == kEnc ? (int)get_option(RSE_OPT_SUB_DEPTH) : 1;
   if (sub_depth > 1) s += kJitSubSource;
   if (kind == kJitWide) {
     // one code struct per wave's share of the outputs, and the kernel (the
     // launch takes W from the build: the options may change meanwhile)
     const int W = wide_waves(p, field);
     if (wide_w) *wide_w = W;
-    const bool shared = W > 1 && get_option(14) != 0;  // RSE_OPT_WIDE_LDS
+    const bool shared = W > 1 && get_option(RSE_OPT_WIDE_LDS) != 0;
     // GF(2^8) networks over pairs of inputs (RSE_OPT_WIDE_PAIRS): the LDS
     // kernels code a round's inputs two at a time, so W must be even
-    const bool pairs = field == 8 && shared && W % 2 == 0 && get_option(29) != 0;
+    const bool pairs = field == 8 && shared && W % 2 == 0 && get_option(RSE_OPT_WIDE_PAIRS) != 0;
     // RSE_OPT_WIDE_HALF: the paired GF(2^8) networks on 2 KiB chunks, one plane
     // group per lane (rse_bitslice_core.hpp wide_body_half: half the
     // accumulators; 8 outputs per wave no longer spill)
-    const bool half = pairs && get_option(38) != 0;
+    const bool half = pairs && get_option(RSE_OPT_WIDE_HALF) != 0;
     if (wide_half) *wide_half = half;
     for (int w = 0; w < W; ++w) {
       uint32_t o0, n;
@@ -263,8 +267,8 @@ std::string make_source(int field, uint32_t k, uint32_t p, const std::vector<uin
       // an input feeds many outputs here: shared temporaries in both fields
       // (GF(2^8): per input or input pair, computed per plane group)
       emit_code(s, name, field, k, n, sub,
-                field == 16 ? (int)get_option(13)
-                            : std::min(pairs ? 32 : 16, (int)get_option(13)),
+                field == 16 ? (int)get_option(RSE_OPT_JIT_CSE)
+                            : std::min(pairs ? 32 : 16, (int)get_option(RSE_OPT_JIT_CSE)),
                 pairs);
     }
     char buf[512];
@@ -293,12 +297,12 @@ std::string make_source(int field, uint32_t k, uint32_t p, const std::vector<uin
           std::snprintf(buf, sizeof buf,
                         "    case %d: rse::wide_body_half<rse::JitWide%d, %u, %d, %d, %d, "
                         "WideArgs, %du>(a, lds); break;\n",
-                        w, w, o0, W, w, (int)get_option(26), 1024 * q);
+                        w, w, o0, W, w, (int)get_option(RSE_OPT_WIDE_DEPTH), 1024 * q);
         else if (shared)
           std::snprintf(buf, sizeof buf,
                         "    case %d: rse::wide_body_lds_deep<rse::JitWide%d, %u, %d, %d, %d, "
                         "WideArgs, %du>(a, lds); break;\n",
-                        w, w, o0, W, w, (int)get_option(26), 1024 * q);
+                        w, w, o0, W, w, (int)get_option(RSE_OPT_WIDE_DEPTH), 1024 * q);
         else
           std::snprintf(buf, sizeof buf,
                         "    case %d: rse::wide_body<rse::JitWide%d, %u, WideArgs, %du>(a); "
@@ -313,7 +317,9 @@ std::string make_source(int field, uint32_t k, uint32_t p, const std::vector<uin
   // GF(2^8) temporaries only above 4 outputs (2 waves/SIMD: room for them; at
   // 3 waves/SIMD the extra live sources would cost spills)
   emit_code(s, "JitCode", field, k, p, rows,
-            field == 16 ? (int)get_option(13) : p > 4 ? std::min(16, (int)get_option(13)) : 0);
+            field == 16 ? (int)get_option(RSE_OPT_JIT_CSE)
+            : p > 4     ? std::min(16, (int)get_option(RSE_OPT_JIT_CSE))
+                        : 0);
   char buf[512];
   if (stage == kEnc) {
     // encode/verify kernels (16 KiB and 4 KiB chunks); a later block of a wide
@@ -362,11 +368,11 @@ std::string make_source(int field, uint32_t k, uint32_t p, const std::vector<uin
   }
   int ns[5];
   const int n = recon_ns(p, ns);
-  const int depth = (int)std::min<int64_t>(3, get_option(27));  // RSE_OPT_RECON_DEPTH
+  const int depth = (int)std::min<int64_t>(3, get_option(RSE_OPT_RECON_DEPTH));
   // 8 sigma rows on wave pairs (RSE_OPT_RECON_PAIRS): 8 KiB units, 3 waves
   // per SIMD; the launchers' grid-stride loops cover either unit size
   // (two pairs per 256-lane workgroup: the launchers' block size)
-  const bool pairs = get_option(28) != 0 && depth <= 1 && p >= 8;
+  const bool pairs = get_option(RSE_OPT_RECON_PAIRS) != 0 && depth <= 1 && p >= 8;
   for (int q = 0; q < n; ++q) {
     const int wpe = ns[q] > 4 ? 2 : 3;
     if (pairs && ns[q] == 8) {
@@ -569,7 +575,7 @@ bool build_with_helper(const std::string& src, const std::string& key, int slot,
   const bool exited = w == pid && WIFEXITED(status);
   if (exited && WEXITSTATUS(status) == 0 && read_file(out_path, &out->code)) {
     out->ok = true;
-    if (cache_dir().empty() || get_option(15) == 0 ||
+    if (cache_dir().empty() || get_option(RSE_OPT_JIT_DISK_CACHE) == 0 ||
         rename(out_path.c_str(), (cache_dir() + "/" + key + ".co").c_str()) != 0)
       unlink(out_path.c_str());
     return true;
@@ -608,7 +614,7 @@ std::shared_ptr<const Compiled> compile(const Entry& e, int stage, int slot) {
       make_source(e.field, e.k, e.p, e.rows, stage, e.kind, &out->wide_w, &out->wide_half);
   const auto t0 = std::chrono::steady_clock::now();
   const std::string key = hash_key(src);
-  const bool disk = get_option(15) != 0 && !cache_dir().empty();
+  const bool disk = get_option(RSE_OPT_JIT_DISK_CACHE) != 0 && !cache_dir().empty();
   if (disk && read_file(cache_dir() + "/" + key + ".co", &out->code)) {
     out->ok = true;
     ++g_cache_hits;
@@ -820,7 +826,7 @@ struct WideBlock {
 // A chain's length over k inputs for p outputs, or 0; fits: also when one
 // module would hold them (an output group with k past the block limit).
 uint32_t chain_len(uint32_t k, uint32_t p, bool fits) {
-  const int64_t lim = get_option(46);
+  const int64_t lim = get_option(RSE_OPT_WIDE_BLOCK_INPUTS);
   if (lim <= 0 || k == 0 || p == 0 || (!fits && wide_eligible(k, p)) || 3u * p >= kWideMaxPtrs)
     return 0;
   const uint32_t kmax = (uint32_t)std::min<int64_t>(lim, (int64_t)(kWideMaxPtrs - 3u * p));
@@ -833,7 +839,7 @@ uint32_t chain_len(uint32_t k, uint32_t p, bool fits) {
 }
 
 bool wide_blocks_plan_impl(uint32_t k, uint32_t p, uint32_t* nb) {
-  const int64_t lim = get_option(46);
+  const int64_t lim = get_option(RSE_OPT_WIDE_BLOCK_INPUTS);
   if (lim <= 0 || k == 0 || p == 0 || wide_eligible(k, p) || 3u * p >= kWideMaxPtrs) return false;
   const uint32_t kmax = (uint32_t)std::min<int64_t>(lim, (int64_t)(kWideMaxPtrs - 3u * p));
   const uint32_t n = (k + kmax - 1) / kmax;
@@ -877,7 +883,7 @@ bool wide_groups_of(uint32_t k, uint32_t p, std::vector<std::array<uint32_t, 3>>
     g->push_back({0u, p, nb});
     return true;
   }
-  const int64_t lim = get_option(46);
+  const int64_t lim = get_option(RSE_OPT_WIDE_BLOCK_INPUTS);
   if (lim <= 0 || k == 0 || p <= kJitMaxOut * 8u || wide_eligible(k, p)) return false;
   const uint32_t G = (p + kJitMaxOut * 8u - 1) / (kJitMaxOut * 8u), base = p / G, extra = p % G;
   uint32_t o0 = 0;
@@ -920,8 +926,9 @@ std::vector<WideBlock> wide_plan_blocks(uint32_t k, uint32_t p, const uint16_t* 
 }  // namespace
 
 int jit_register(int field, uint32_t k, uint32_t p, const uint16_t* rows, JitKind kind) {
-  if (get_option(9) == 0 || (field != 8 && field != 16) || k == 0 || k > (uint32_t)kMaxIn ||
-      p == 0 || p > kJitMaxOut || (kind == kJitCodec && bitslice_compiled(field, k, p)))
+  if (get_option(RSE_OPT_JIT) == 0 || (field != 8 && field != 16) || k == 0 ||
+      k > (uint32_t)kMaxIn || p == 0 || p > kJitMaxOut ||
+      (kind == kJitCodec && bitslice_compiled(field, k, p)))
     return 0;
   registry();
   Worker& w = worker();
@@ -931,7 +938,7 @@ int jit_register(int field, uint32_t k, uint32_t p, const uint16_t* rows, JitKin
   // under RSE_OPT_JIT 2, where the caller waits for this very build
   if (kind == kJitPattern &&
       (g_patterns >= max_patterns() ||
-       (get_option(9) < 2 && g_jobs[kEnc].size() >= kMaxPendingPatternJobs)))
+       (get_option(RSE_OPT_JIT) < 2 && g_jobs[kEnc].size() >= kMaxPendingPatternJobs)))
     return 0;
   if ((kind == kJitBlock || kind == kJitBlockAcc) && g_blocks >= kMaxBlocks) return 0;
   add_locked(field, k, p, rows, k, kind);
@@ -941,7 +948,7 @@ int jit_register(int field, uint32_t k, uint32_t p, const uint16_t* rows, JitKin
 }
 
 int jit_register_blocks(int field, uint32_t k, uint32_t p, const uint16_t* rows, bool pattern) {
-  if (get_option(9) == 0 || (field != 8 && field != 16) || k == 0 || p == 0) return 0;
+  if (get_option(RSE_OPT_JIT) == 0 || (field != 8 && field != 16) || k == 0 || p == 0) return 0;
   registry();
   Worker& w = worker();
   std::vector<std::array<uint32_t, 3>> groups;
@@ -986,7 +993,7 @@ int jit_register_blocks(int field, uint32_t k, uint32_t p, const uint16_t* rows,
 }
 
 uint32_t wide_per_wave() {
-  const int64_t v = get_option(18);
+  const int64_t v = get_option(RSE_OPT_WIDE_SPLIT);
   return v >= 2 && v <= (int64_t)kJitMaxOut ? (uint32_t)v : kJitMaxOut;
 }
 
@@ -1002,7 +1009,7 @@ bool wide_eligible(uint32_t k, uint32_t p) {
 }
 
 int jit_register_wide(int field, uint32_t k, uint32_t p, const uint16_t* rows, bool pattern) {
-  if (get_option(9) == 0 || (field != 8 && field != 16) || !wide_eligible(k, p)) return 0;
+  if (get_option(RSE_OPT_JIT) == 0 || (field != 8 && field != 16) || !wide_eligible(k, p)) return 0;
   registry();
   Worker& w = worker();
   std::lock_guard<std::mutex> g(g_mu);
@@ -1028,11 +1035,13 @@ hipError_t launch_wide(int field, uint32_t k, uint32_t p, const uint16_t* rows,
                        uint32_t* mismatch, bool per_stripe, hipStream_t stream, uint64_t* done) {
   *done = 0;
   // shards of exactly 1 or 2 KiB: 4 or 2 stripes per 4 KiB chunk (SUB)
-  const int subq = (len == 1024u || len == 2048u) && get_option(33) != 0 ? (int)(len / 1024u) : 0;
+  const int subq = (len == 1024u || len == 2048u) && get_option(RSE_OPT_SUB_CHUNKS) != 0
+                       ? (int)(len / 1024u)
+                       : 0;
   const uint64_t cps = len / 4096u;
   if ((cps == 0 && !subq) || n_stripes == 0) return hipSuccess;
   Entry* e = find_entry(field, k, p, rows, k, kJitWide);
-  if (!e || status_of(e, get_option(9) >= 2) != 2) return hipSuccess;
+  if (!e || status_of(e, get_option(RSE_OPT_JIT) >= 2) != 2) return hipSuccess;
   const std::shared_ptr<const Compiled> c = e->built[kEnc].get();
   int dev = 0;
   hipError_t he = hipGetDevice(&dev);
@@ -1101,7 +1110,7 @@ hipError_t launch_wide(int field, uint32_t k, uint32_t p, const uint16_t* rows,
   // 1 / 2 KiB shards, 4096 (2048) / len stripes per chunk
   const uint64_t cb = c->wide_half ? 2048u : 4096u, spc = cb / (subq ? len : cb);
   const uint64_t total = subq ? (n_stripes + spc - 1) / spc : cps * (4096u / cb) * n_stripes;
-  const int64_t grid = get_option(2);
+  const int64_t grid = get_option(RSE_OPT_GRID_X);
   // tools/tune.py grid sweeps, 128 stripes x 1 MiB (profiles/r04/s2/): GF(2^16)
   // 40+12 16384 workgroups 5.29 TB/s against 5.05 at 4096; GF(2^8) 50+20 flat
   // from 2048 to 8192 (4.72), 4.68 at 16384
@@ -1112,7 +1121,7 @@ hipError_t launch_wide(int field, uint32_t k, uint32_t p, const uint16_t* rows,
   // workgroup starting cold (same box, profiles/r05/s45/g*.log: 32+32 x 1 KiB
   // 4.01 -> 4.22 TB/s, 64+64 2.49 -> 2.57, 50+20 4.53 -> 4.58; 16+16 5.78 ->
   // 5.32 and the 1 MiB codecs 5-7 % slower, so not for those); -1 fixed counts
-  int64_t mult = get_option(44);
+  int64_t mult = get_option(RSE_OPT_WIDE_GRID);
   if (mult == 0) mult = (subq && (uint64_t)k * p >= 1000u) ? 1 : -1;
   uint64_t gx = grid > 0                ? (uint64_t)grid
                 : (mult > 0 && cap > 0) ? (uint64_t)mult * cap
@@ -1170,7 +1179,7 @@ hipError_t launch_wide_blocks(int field, uint32_t k, uint32_t p, const uint16_t*
   std::vector<std::array<uint32_t, 3>> groups;
   if (!wide_groups_of(k, p, &groups) || n_stripes == 0) return hipSuccess;
   const std::vector<WideBlock> bl = wide_plan_blocks(k, p, rows, groups);
-  const bool wait = get_option(9) >= 2;
+  const bool wait = get_option(RSE_OPT_JIT) >= 2;
   for (const WideBlock& b : bl)  // every module built, or none is launched
     if (status_of(find_entry(field, b.kk, b.np, b.rows.data(), b.kk, kJitWide), wait) != 2)
       return hipSuccess;
@@ -1207,7 +1216,7 @@ int jit_status(int field, uint32_t k, uint32_t p, const uint16_t* rows, bool wai
 bool jit_find(int field, uint32_t k, uint32_t p, const uint16_t* rows, size_t stride, int stage,
               JitFns* out, hipError_t* err, bool acc) {
   *err = hipSuccess;
-  const int64_t mode = get_option(9);
+  const int64_t mode = get_option(RSE_OPT_JIT);
   if (mode == 0 || p > kJitMaxOut || (acc && stage != kEnc)) return false;
   Entry* e = find_entry(field, k, p, rows, stride, acc ? (int)kJitBlockAcc : -2);
   if (!e || stage >= e->stages) return false;

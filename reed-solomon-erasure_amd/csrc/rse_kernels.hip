@@ -23,10 +23,12 @@
 // (galois_16.rs:146-162 with reduce_from :97-107 folded in), so a GF(2^16)
 // shard is two GF(2^8) byte planes and one GF(2^16) coefficient is a 2x2 block
 // of GF(2^8) coefficients.  Planes are split/merged in registers with v_perm.
+#include <array>
 #include <cstdarg>
 #include <cstdio>
 
 #include "rse_device.hpp"
+#include "rse_options.hpp"
 
 namespace rse {
 namespace {
@@ -764,57 +766,121 @@ const Variant* pick(int field, const CodeArgs& a, int64_t variant) {
   return &g[no <= 2 ? 0 : no <= 4 ? 1 : no <= 8 ? 2 : 3];
 }
 
-// Launch-shape options (rse_set_option).  Defaults come from in-process A/B
-// sweeps on MI355X (tools/tune.py; DESIGN.md "Launch shape").
-struct Options {
-  int64_t nontemporal = 1;        // streaming hint on shard loads/stores
-  int64_t grid_x = 0;             // blocks per stripe row (0 = auto)
-  int64_t stripes_in_flight = 0;  // gridDim.y (0 = all stripes at once)
-  int64_t variant = -1;           // kernel variant of a tuned shape (-1 = default)
-  int64_t bitslice = 1;           // bit-sliced kernels where compiled (rse_bitslice.hip)
-  int64_t host_chunk_kib = 4096;  // host pipeline chunk per shard (rse_encode_host*)
-  int64_t host_h2d_streams = 2;   // host pipeline H2D streams (tools/host_e2e.py)
-  int64_t jit = 1;                // run-time specialised bit-sliced kernels (rse_jit.cpp)
-  int64_t jit_patterns = 1;       // ... also for repeated decode patterns
-  int64_t jit_cse = 32;           // GF(2^16) specialised networks: temporaries per input
-  int64_t wide_lds = 1;           // wide modules: slicing shared through LDS
-  int64_t jit_disk_cache = 1;     // run-time specialised modules cached on disk
-  int64_t recon_mix = 3;          // syndrome reconstruct mixing: 3/2 Horner (4 steps per word / 1), 1 doubling chains, 0 tables
-  int64_t wide_split = 0;         // outputs per wave of wide modules (0: auto, rse_jit.cpp wide_waves)
-  int64_t wide_balance = 1;       // wide modules: waves per workgroup rounded to 2, 4, 8
-  int64_t wide_occupancy = 0;     // wide modules: waves per SIMD compiled for (0 = auto)
-  int64_t host_copy_2d = 1;       // host pipeline: 2D copies for runs of a flat buffer's shards
-  int64_t jit_exact = 1;          // run-time networks: exact-decomposition temporaries
-  int64_t wide_depth = 1;         // wide modules: inputs in flight per wave (1..4)
-  int64_t recon_depth = 1;        // syndrome reconstruct: inputs in flight per lane (1..4)
-  int64_t recon_pairs = 8;        // syndrome reconstruct at 8 sigma rows on wave pairs (8: by field)
-  int64_t wide_pairs = 1;         // wide GF(2^8) modules: networks over pairs of inputs
-  int64_t sync_event = 0;         // verify calls wait on an event, not the stream (A/B)
-  int64_t spin_wait = 1;          // one-launch verifies: poll the completion word (A/B)
-  int64_t host_direct = 1;        // small one-stripe host calls: one staging buffer (A/B)
-  int64_t sub_chunks = 1;         // 1 / 2 KiB shards on the bit-sliced kernels (A/B)
-  int64_t subfield = 1;           // GF(2^16) codecs of <= 256 shards code in GF(2^8) (A/B)
-  int64_t jit_max_patterns = 64;  // decode-pattern modules per process
-  int64_t jit_max_pattern_blocks = 64;  // blocks of wide decode patterns per process
-  int64_t recon_w4_min = 64;      // 4 KiB syndrome chunks from this many coefficients
-  int64_t wide_half = 1;          // GF(2^8) paired wide modules on 2 KiB chunks (one plane group)
-  int64_t dispatch = 1;           // *_now calls on the resident dispatcher (rse_dispatch.hip)
-  int64_t dispatch_idle_us = 200;  // the resident kernel ends after this long without a call
-  int64_t dispatch_max_bytes = 65536;  // shard bytes up to which a *_now call is dispatched
-  int64_t wide_grid = 0;          // wide launches: -1 fixed workgroup counts, m > 0 m x resident, 0 auto
-  int64_t dispatch_wgs = 8;       // workgroups of the resident dispatcher
-  int64_t wide_block_inputs = 128;  // data inputs per wide module of a chain (0: 8 x 32 blocks)
-  int64_t dispatch_lane_units = 1;  // dispatcher: (vector, output) units per lane per workgroup
-  int64_t sub_depth = 4;  // narrow modules' 1 / 2 KiB-shard kernels: inputs in flight per wave
-  int64_t tune_nosync = 0;  // RSE_TUNE_SPLITS builds: wide modules without barriers (timing)
-  int64_t fft = 1;  // GF(2^8) k = p = 16 / 32 / 64 (2: and 128) codecs on the additive-FFT kernels (rse_fft.hip)
-  int64_t host_queues = 1;  // host pipeline: 1 the D2H stream at high priority, 0 plain (A/B)
-  int64_t host_zc_out = 1;  // host pipeline: outputs stored in place in mapped pinned memory
-  int64_t ticket_grid = 1;  // ticket kernels (rse_bitslice_ticket.hpp): workgroups = this x resident
-  int64_t fft16 = 0;  // GF(2^16) codecs past 256 shards with 2^m - k <= 32 on the pruned-FFT kernel (rse_fft16.hip)
+// ---------------------------------------------------------------------------
+// The library's options (rse_set_option / rse_get_option): one row per key --
+// its default, what it stores for a value set, and whether a caller may set it
+// without RSE_TUNE=1.  A new option is one row here and one #define in
+// include/rse_hip.h (kCaller) or include/rse_hip_tune.h.  Defaults come from
+// in-process A/B sweeps on MI355X (tools/tune.py; DESIGN.md "Launch shape").
+thread_local int64_t g_bs_launches = 0;  // bit-sliced launches on this thread
+int64_t bitslice_launches() { return g_bs_launches; }
+
+constexpr int64_t kOptRefuse = INT64_MIN;  // a rule(fn)'s answer: refuse the value, keep the setting
+constexpr int64_t clamp_to(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : v > hi ? hi : v; }
+int64_t wide_split_rule(int64_t v) { return v <= 0 ? 0 : clamp_to(v, 2, 8); }
+int64_t wide_occupancy_rule(int64_t v) { return v == 1 ? 2 : clamp_to(v, 0, 4); }
+int64_t recon_pairs_rule(int64_t v) {
+#ifndef RSE_TUNE_SPLITS
+  // 4 / 5 select the timing splits, which write wrong bytes: tools/tune.py's
+  // -DRSE_TUNE_SPLITS build only (rse_bitslice.hip RSE_SPLIT_FN)
+  if (v == 4 || v == 5) return kOptRefuse;
+#endif
+  return clamp_to(v, 0, 8);
+}
+int64_t fft_rule(int64_t v) { return v == 0 || v == 2 ? v : 1; }
+
+struct OptRule {
+  enum Kind : uint8_t { kNone, kFlag, kClamp, kFn, kCounter } kind = kNone;
+  int64_t lo = 0, hi = 0;            // kClamp
+  int64_t (*fn)(int64_t) = nullptr;  // kFn: the value stored for the one set
+  int64_t (*read)() = nullptr;       // kCounter: a read-only key
 };
-thread_local int64_t g_bs_launches = 0;  // bit-sliced launches on this thread (RSE_OPT 6)
-Options g_opt;
+constexpr OptRule flag() { return {OptRule::kFlag}; }  // value ? 1 : 0
+constexpr OptRule clamp(int64_t lo, int64_t hi) { return {OptRule::kClamp, lo, hi}; }
+constexpr OptRule at_least(int64_t lo) { return clamp(lo, INT64_MAX); }
+constexpr OptRule any() { return clamp(INT64_MIN, INT64_MAX); }
+constexpr OptRule rule(int64_t (*fn)(int64_t)) { return {OptRule::kFn, 0, 0, fn}; }
+constexpr OptRule counter(int64_t (*read)()) { return {OptRule::kCounter, 0, 0, nullptr, read}; }
+
+struct OptionRow {
+  int key;
+  int64_t def;
+  OptRule rule;
+  bool caller = false;  // include/rse_hip.h's keys; the others are rse_hip_tune.h's switches
+};
+constexpr bool kCaller = true;
+
+constexpr OptionRow kOptionRows[] = {
+    {RSE_OPT_NONTEMPORAL, 1, flag()},         // streaming hint on shard loads/stores
+    {RSE_OPT_GRID_X, 0, at_least(0)},         // blocks per stripe row (0 = auto)
+    {RSE_OPT_STRIPES_IN_FLIGHT, 0, at_least(0)},  // gridDim.y (0 = all stripes at once)
+    {RSE_OPT_KERNEL_VARIANT, -1, any()},      // kernel variant of a tuned shape (-1 = default)
+    {RSE_OPT_BITSLICE, 1, flag()},            // bit-sliced kernels where compiled (rse_bitslice.hip)
+    {RSE_OPT_BITSLICE_LAUNCHES, 0, counter(bitslice_launches)},
+    {RSE_OPT_HOST_CHUNK_KIB, 4096, at_least(64), kCaller},  // host pipeline chunk per shard
+    {RSE_OPT_HOST_H2D_STREAMS, 2, clamp(1, 4), kCaller},  // host pipeline H2D streams (tools/host_e2e.py)
+    {RSE_OPT_JIT, 1, clamp(0, 2), kCaller},   // run-time specialised bit-sliced kernels (rse_jit.cpp)
+    {RSE_OPT_JIT_MODULES, 0, counter(jit_modules_built)},
+    {RSE_OPT_JIT_PATTERNS, 1, flag(), kCaller},  // ... also for repeated decode patterns
+    {RSE_OPT_JIT_CSE, 32, clamp(0, 32)},      // GF(2^16) specialised networks: temporaries per input
+    {RSE_OPT_WIDE_LDS, 1, flag()},            // wide modules: slicing shared through LDS
+    {RSE_OPT_JIT_DISK_CACHE, 1, flag(), kCaller},  // run-time specialised modules cached on disk
+    {RSE_OPT_JIT_CACHE_HITS, 0, counter(jit_cache_hits)},
+    {RSE_OPT_RECON_MIX, 3, clamp(0, 3)},  // syndrome reconstruct mixing: 3/2 Horner (4 steps per word / 1), 1 doubling chains, 0 tables
+    {RSE_OPT_WIDE_SPLIT, 0, rule(wide_split_rule)},  // outputs per wave of wide modules (0: auto, rse_jit.cpp wide_waves)
+    {RSE_OPT_WIDE_BALANCE, 1, flag()},        // wide modules: waves per workgroup rounded to 2, 4, 8
+    {RSE_OPT_WIDE_OCCUPANCY, 0, rule(wide_occupancy_rule)},  // wide modules: waves per SIMD compiled for (0 = auto)
+    {RSE_OPT_HOST_COPY_2D, 1, flag()},  // host pipeline: 2D copies for runs of a flat buffer's shards
+    {RSE_OPT_JIT_EXACT, 1, flag()},           // run-time networks: exact-decomposition temporaries
+    {RSE_OPT_WIDE_DEPTH, 1, clamp(1, 4)},     // wide modules: inputs in flight per wave
+    {RSE_OPT_RECON_DEPTH, 1, clamp(1, 4)},    // syndrome reconstruct: inputs in flight per lane
+    {RSE_OPT_RECON_PAIRS, 8, rule(recon_pairs_rule)},  // syndrome reconstruct at 8 sigma rows on wave pairs (8: by field)
+    {RSE_OPT_WIDE_PAIRS, 1, flag()},          // wide GF(2^8) modules: networks over pairs of inputs
+    {RSE_OPT_SYNC_EVENT, 0, flag()},   // verify calls wait on an event, not the stream (A/B)
+    {RSE_OPT_SPIN_WAIT, 1, flag()},    // one-launch verifies: poll the completion word (A/B)
+    {RSE_OPT_HOST_DIRECT, 1, flag()},  // small one-stripe host calls: one staging buffer (A/B)
+    {RSE_OPT_SUB_CHUNKS, 1, flag()},   // 1 / 2 KiB shards on the bit-sliced kernels (A/B)
+    {RSE_OPT_SUBFIELD, 1, flag()},     // GF(2^16) codecs of <= 256 shards code in GF(2^8) (A/B)
+    {RSE_OPT_JIT_MAX_PATTERNS, 64, at_least(0), kCaller},  // decode-pattern modules per process
+    {RSE_OPT_JIT_MAX_PATTERN_BLOCKS, 64, at_least(0), kCaller},  // blocks of wide decode patterns per process
+    {RSE_OPT_RECON_W4_MIN, 64, at_least(0)},  // 4 KiB syndrome chunks from this many coefficients
+    {RSE_OPT_WIDE_HALF, 1, flag()},  // GF(2^8) paired wide modules on 2 KiB chunks (one plane group)
+    {RSE_OPT_DISPATCH, 1, flag(), kCaller},  // *_now calls on the resident dispatcher (rse_dispatch.hip)
+    {RSE_OPT_DISPATCH_IDLE_US, 200, clamp(10, 1000000), kCaller},  // the resident kernel ends after this long without a call
+    {RSE_OPT_DISPATCH_MAX_BYTES, 65536, at_least(0), kCaller},  // shard bytes up to which a *_now call is dispatched
+    {RSE_OPT_WIDE_GRID, 0, clamp(-1, 64)},  // wide launches: -1 fixed workgroup counts, m > 0 m x resident, 0 auto
+    {RSE_OPT_DISPATCH_WORKGROUPS, 8, clamp(1, 64), kCaller},  // workgroups of the resident dispatcher
+    {RSE_OPT_WIDE_BLOCK_INPUTS, 128, at_least(0)},  // data inputs per wide module of a chain (0: 8 x 32 blocks)
+#ifdef RSE_TUNE_SPLITS
+    {RSE_OPT_TUNE_NOSYNC, 0, flag()},  // wide modules without barriers (timing; rse_jit.cpp make_source)
+#endif
+    {RSE_OPT_DISPATCH_LANE_UNITS, 1, clamp(1, 64)},  // dispatcher: (vector, output) units per lane per workgroup
+    {RSE_OPT_SUB_DEPTH, 4, clamp(1, 4)},  // narrow modules' 1 / 2 KiB-shard kernels: inputs in flight per wave
+    {RSE_OPT_FFT, 1, rule(fft_rule)},  // GF(2^8) k = p = 16 / 32 / 64 (2: and 128) codecs on the additive-FFT kernels (rse_fft.hip)
+    {RSE_OPT_HOST_QUEUES, 1, flag()},  // host pipeline: 1 the D2H stream at high priority, 0 plain (A/B)
+    {RSE_OPT_HOST_ZC_OUT, 1, flag()},  // host pipeline: outputs stored in place in mapped pinned memory
+    {RSE_OPT_FFT16, 0, flag()},  // GF(2^16) codecs past 256 shards with 2^m - k <= 32 on the pruned-FFT kernel (rse_fft16.hip)
+    {RSE_OPT_TICKET_GRID, 1, clamp(1, 16)},  // ticket kernels (rse_bitslice_ticket.hpp): workgroups = this x resident
+};
+
+// The rows by key, and every key's value: -1, get_option's answer for a key
+// that does not exist, where there is no row.
+constexpr int kOptionKeys = 56;
+struct OptionTable {
+  OptionRow row[kOptionKeys] = {};
+  std::array<int64_t, kOptionKeys> def = {};
+};
+constexpr OptionTable option_table() {
+  OptionTable t;
+  for (int64_t& v : t.def) v = -1;
+  for (const OptionRow& r : kOptionRows) {
+    t.row[r.key] = r;
+    t.def[r.key] = r.def;
+  }
+  return t;
+}
+constexpr OptionTable kOptions = option_table();
+std::array<int64_t, kOptionKeys> g_opt = kOptions.def;
 thread_local char g_last_kernel[128] = "";  // rse_last_kernel()
 
 // ---------------------------------------------------------------------------
@@ -1138,11 +1204,11 @@ hipError_t launch_code(int field, const CodeArgs& args, hipStream_t stream) {
   if (args.n_in == 0 || args.n_in > (uint32_t)kMaxIn || args.n_out == 0 ||
       args.n_out > (uint32_t)kMaxOut || args.n_stripes == 0)
     return hipErrorInvalidValue;
-  if (g_opt.bitslice) {
+  if (g_opt[RSE_OPT_BITSLICE]) {
     bool handled = false;
     uint64_t done = 0;
-    hipError_t e = launch_bitslice(field, args, g_opt.nontemporal != 0, g_opt.grid_x, stream,
-                                   &handled, &done);
+    hipError_t e = launch_bitslice(field, args, g_opt[RSE_OPT_NONTEMPORAL] != 0,
+                                   g_opt[RSE_OPT_GRID_X], stream, &handled, &done);
     if (e != hipSuccess) return e;
     if (handled) {
       ++g_bs_launches;
@@ -1167,11 +1233,13 @@ hipError_t launch_code(int field, const CodeArgs& args, hipStream_t stream) {
 }
 
 hipError_t launch_table(int field, const CodeArgs& args, hipStream_t stream) {
-  const Variant* var = pick(field, args, g_opt.variant);
-  KernelFn fn = var->fn[g_opt.nontemporal ? 1 : 0];
+  const int64_t nt = g_opt[RSE_OPT_NONTEMPORAL], in_flight = g_opt[RSE_OPT_STRIPES_IN_FLIGHT],
+                grid_x = g_opt[RSE_OPT_GRID_X];
+  const Variant* var = pick(field, args, g_opt[RSE_OPT_KERNEL_VARIANT]);
+  KernelFn fn = var->fn[nt ? 1 : 0];
   note_kernel("table gf%d %u+%u %s nt%d", field, args.n_in, args.n_out,
-              var->pipe ? "pipe" : "fused", (int)g_opt.nontemporal);
-  uint64_t gy = g_opt.stripes_in_flight > 0 ? (uint64_t)g_opt.stripes_in_flight : args.n_stripes;
+              var->pipe ? "pipe" : "fused", (int)nt);
+  uint64_t gy = in_flight > 0 ? (uint64_t)in_flight : args.n_stripes;
   if (gy > args.n_stripes) gy = args.n_stripes;
   if (gy > 65535) gy = 65535;
   if (var->pipe) gy = 1;
@@ -1180,7 +1248,7 @@ hipError_t launch_table(int field, const CodeArgs& args, hipStream_t stream) {
   // ~2048 workgroups over the chip in total, never more per stripe row than
   // the row has vectors for (idle workgroups still build their LDS tables:
   // 16 per row at 1 KiB shards ran 13x slower than 1, tools/small_session.sh)
-  uint64_t gx = g_opt.grid_x > 0 ? (uint64_t)g_opt.grid_x : (2048u + gy - 1) / gy;
+  uint64_t gx = grid_x > 0 ? (uint64_t)grid_x : (2048u + gy - 1) / gy;
   if (gx > want) gx = want;
   if (gx < 1) gx = 1;
   hipLaunchKernelGGL(fn, dim3((uint32_t)gx, (uint32_t)gy, 1), dim3(kBlock, 1, 1), 0, stream, args);
@@ -1297,9 +1365,10 @@ hipError_t launch_recon_plan(int field, const uint16_t* d_parity, const uint8_t*
   const uint64_t want = (units + kBlock - 1) / kBlock;
   if (gx > want) gx = want;
   if (gx < 1) gx = 1;
+  const bool nt = g_opt[RSE_OPT_NONTEMPORAL] != 0;
   void (*fn)(const CodeArgs*) =
-      field == 8 ? (g_opt.nontemporal ? gf8_code_desc_kernel<true> : gf8_code_desc_kernel<false>)
-                 : (g_opt.nontemporal ? gf16_code_desc_kernel<true> : gf16_code_desc_kernel<false>);
+      field == 8 ? (nt ? gf8_code_desc_kernel<true> : gf8_code_desc_kernel<false>)
+                 : (nt ? gf16_code_desc_kernel<true> : gf16_code_desc_kernel<false>);
   note_kernel("table-desc gf%d %u+%u", field, k, T - k);
   for (uint32_t ib = 0; ib < n_ib; ++ib)  // later input blocks accumulate: stream order
     for (uint64_t y0 = 0; y0 < rows; y0 += 65535u) {
@@ -1313,63 +1382,23 @@ hipError_t launch_recon_plan(int field, const uint16_t* d_parity, const uint8_t*
 }
 
 int set_option(int key, int64_t value) {
-  switch (key) {
-    case 1: g_opt.nontemporal = value ? 1 : 0; return 0;
-    case 2: g_opt.grid_x = value < 0 ? 0 : value; return 0;
-    case 3: g_opt.stripes_in_flight = value < 0 ? 0 : value; return 0;
-    case 4: g_opt.variant = value; return 0;
-    case 5: g_opt.bitslice = value ? 1 : 0; return 0;
-    case 7: g_opt.host_chunk_kib = value < 64 ? 64 : value; return 0;
-    case 8: g_opt.host_h2d_streams = value < 1 ? 1 : value > 4 ? 4 : value; return 0;
-    case 9: g_opt.jit = value < 0 ? 0 : value > 2 ? 2 : value; return 0;
-    case 11: g_opt.jit_patterns = value ? 1 : 0; return 0;
-    case 13: g_opt.jit_cse = value < 0 ? 0 : value > 32 ? 32 : value; return 0;
-    case 14: g_opt.wide_lds = value ? 1 : 0; return 0;
-    case 15: g_opt.jit_disk_cache = value ? 1 : 0; return 0;
-    case 17: g_opt.recon_mix = value < 0 ? 0 : value > 3 ? 3 : value; return 0;
-    case 18: g_opt.wide_split = value <= 0 ? 0 : value < 2 ? 2 : value > 8 ? 8 : value; return 0;
-    case 19: g_opt.wide_balance = value ? 1 : 0; return 0;
-    case 20: g_opt.wide_occupancy = value < 0 ? 0 : value > 4 ? 4 : value == 1 ? 2 : value; return 0;
-    case 21: g_opt.host_copy_2d = value ? 1 : 0; return 0;
-    case 23: g_opt.jit_exact = value ? 1 : 0; return 0;
-    case 26: g_opt.wide_depth = value < 1 ? 1 : value > 4 ? 4 : value; return 0;
-    case 27: g_opt.recon_depth = value < 1 ? 1 : value > 4 ? 4 : value; return 0;
-    case 28:
-#ifndef RSE_TUNE_SPLITS
-      // 4 / 5 select the timing splits, which write wrong bytes: tools/tune.py's
-      // -DRSE_TUNE_SPLITS build only (rse_bitslice.hip RSE_SPLIT_FN)
-      if (value == 4 || value == 5) return -2;
-#endif
-      g_opt.recon_pairs = value < 0 ? 0 : value > 8 ? 8 : value;
-      return 0;
-    case 29: g_opt.wide_pairs = value ? 1 : 0; return 0;
-    case 30: g_opt.sync_event = value ? 1 : 0; return 0;
-    case 31: g_opt.spin_wait = value ? 1 : 0; return 0;
-    case 32: g_opt.host_direct = value ? 1 : 0; return 0;
-    case 33: g_opt.sub_chunks = value ? 1 : 0; return 0;
-    case 34: g_opt.subfield = value ? 1 : 0; return 0;
-    case 35: g_opt.jit_max_patterns = value < 0 ? 0 : value; return 0;
-    case 36: g_opt.jit_max_pattern_blocks = value < 0 ? 0 : value; return 0;
-    case 37: g_opt.recon_w4_min = value < 0 ? 0 : value; return 0;
-    case 38: g_opt.wide_half = value ? 1 : 0; return 0;
-    case 39: g_opt.dispatch = value ? 1 : 0; return 0;
-    case 40: g_opt.dispatch_idle_us = value < 10 ? 10 : value > 1000000 ? 1000000 : value; return 0;
-    case 41: g_opt.dispatch_max_bytes = value < 0 ? 0 : value; return 0;
-    case 44: g_opt.wide_grid = value < -1 ? -1 : value > 64 ? 64 : value; return 0;
-    case 45: g_opt.dispatch_wgs = value < 1 ? 1 : value > 64 ? 64 : value; return 0;
-    case 46: g_opt.wide_block_inputs = value < 0 ? 0 : value; return 0;
-    case 49: g_opt.dispatch_lane_units = value < 1 ? 1 : value > 64 ? 64 : value; return 0;
-    case 50: g_opt.sub_depth = value < 1 ? 1 : value > 4 ? 4 : value; return 0;
-    case 51: g_opt.fft = value == 0 || value == 2 ? value : 1; return 0;
-    case 52: g_opt.host_queues = value ? 1 : 0; return 0;
-    case 53: g_opt.host_zc_out = value ? 1 : 0; return 0;
-    case 54: g_opt.fft16 = value ? 1 : 0; return 0;
-    case 55: g_opt.ticket_grid = value < 1 ? 1 : value > 16 ? 16 : value; return 0;
-#ifdef RSE_TUNE_SPLITS
-    case 47: g_opt.tune_nosync = value ? 1 : 0; return 0;  // rse_jit.cpp make_source
-#endif
-    default: return -1;
+  if (key < 0 || key >= kOptionKeys) return -1;
+  const OptRule& r = kOptions.row[key].rule;
+  switch (r.kind) {
+    case OptRule::kFlag: value = value ? 1 : 0; break;
+    case OptRule::kClamp: value = clamp_to(value, r.lo, r.hi); break;
+    case OptRule::kFn:
+      value = r.fn(value);
+      if (value == kOptRefuse) return -2;
+      break;
+    default: return -1;  // no such key, or a read-only one
   }
+  g_opt[key] = value;
+  return 0;
+}
+
+bool caller_may_set_option(int key) {
+  return key >= 0 && key < kOptionKeys && kOptions.row[key].caller;
 }
 
 void count_bitslice_launch() { ++g_bs_launches; }
@@ -1383,59 +1412,9 @@ void note_kernel(const char* fmt, ...) {
 const char* last_kernel() { return g_last_kernel; }
 
 int64_t get_option(int key) {
-  switch (key) {
-    case 1: return g_opt.nontemporal;
-    case 2: return g_opt.grid_x;
-    case 3: return g_opt.stripes_in_flight;
-    case 4: return g_opt.variant;
-    case 5: return g_opt.bitslice;
-    case 6: return g_bs_launches;
-    case 7: return g_opt.host_chunk_kib;
-    case 8: return g_opt.host_h2d_streams;
-    case 9: return g_opt.jit;
-    case 10: return jit_modules_built();
-    case 11: return g_opt.jit_patterns;
-    case 13: return g_opt.jit_cse;
-    case 14: return g_opt.wide_lds;
-    case 15: return g_opt.jit_disk_cache;
-    case 16: return jit_cache_hits();
-    case 17: return g_opt.recon_mix;
-    case 18: return g_opt.wide_split;
-    case 19: return g_opt.wide_balance;
-    case 20: return g_opt.wide_occupancy;
-    case 21: return g_opt.host_copy_2d;
-    case 23: return g_opt.jit_exact;
-    case 26: return g_opt.wide_depth;
-    case 27: return g_opt.recon_depth;
-    case 28: return g_opt.recon_pairs;
-    case 29: return g_opt.wide_pairs;
-    case 30: return g_opt.sync_event;
-    case 31: return g_opt.spin_wait;
-    case 32: return g_opt.host_direct;
-    case 33: return g_opt.sub_chunks;
-    case 34: return g_opt.subfield;
-    case 35: return g_opt.jit_max_patterns;
-    case 36: return g_opt.jit_max_pattern_blocks;
-    case 37: return g_opt.recon_w4_min;
-    case 38: return g_opt.wide_half;
-    case 39: return g_opt.dispatch;
-    case 40: return g_opt.dispatch_idle_us;
-    case 41: return g_opt.dispatch_max_bytes;
-    case 44: return g_opt.wide_grid;
-    case 45: return g_opt.dispatch_wgs;
-    case 46: return g_opt.wide_block_inputs;
-    case 49: return g_opt.dispatch_lane_units;
-    case 50: return g_opt.sub_depth;
-    case 51: return g_opt.fft;
-    case 52: return g_opt.host_queues;
-    case 53: return g_opt.host_zc_out;
-    case 54: return g_opt.fft16;
-    case 55: return g_opt.ticket_grid;
-#ifdef RSE_TUNE_SPLITS
-    case 47: return g_opt.tune_nosync;
-#endif
-    default: return -1;
-  }
+  if (key < 0 || key >= kOptionKeys) return -1;
+  const OptRule& r = kOptions.row[key].rule;
+  return r.kind == OptRule::kCounter ? r.read() : g_opt[key];
 }
 
 hipError_t launch_fill_splitmix(void* dst, uint64_t nbytes, uint64_t seed, uint64_t shard_id,

@@ -368,6 +368,79 @@ def test_wrong_byte_timing_splits_are_refused():
         L.rse_set_option(RECON_PAIRS, old)
 
 
+# Every settable option: its default, and set value -> value read back, below,
+# inside and above its range.  Written out by hand from the rules the keys have
+# had since they were added (they are ABI, like the numbers), never read from
+# the library.
+OPTION_DEFAULTS = {
+    -1: [4],
+    0: [2, 3, 18, 20, 30, 44, 54],
+    1: [1, 5, 9, 11, 14, 15, 19, 21, 23, 26, 27, 29, 31, 32, 33, 34, 38, 39, 49, 51, 52, 53, 55],
+    2: [8], 3: [17], 4: [50], 8: [28, 45], 32: [13], 64: [35, 36, 37], 128: [46], 200: [40],
+    4096: [7], 65536: [41],
+}
+OPTION_FLAGS = [1, 5, 11, 14, 15, 19, 21, 23, 29, 30, 31, 32, 33, 34, 38, 39, 52, 53, 54]
+OPTION_AT_LEAST_0 = [2, 3, 35, 36, 37, 41, 46]
+OPTION_CLAMPS = {8: (1, 4), 9: (0, 2), 13: (0, 32), 17: (0, 3), 26: (1, 4), 27: (1, 4), 50: (1, 4),
+                 40: (10, 1000000), 44: (-1, 64), 45: (1, 64), 49: (1, 64), 55: (1, 16)}
+OPTION_EDGES = {
+    4: [(-7, -7), (0, 0), (1 << 40, 1 << 40)],
+    7: [(1, 64), (-5, 64), (63, 64), (64, 64), (10 ** 9, 10 ** 9)],
+    18: [(-3, 0), (0, 0), (1, 2), (2, 2), (5, 5), (8, 8), (9, 8)],
+    20: [(-1, 0), (0, 0), (1, 2), (2, 2), (3, 3), (4, 4), (5, 4)],
+    28: [(-1, 0), (9, 8), (0, 0), (3, 3), (6, 6), (8, 8)],  # 4 / 5: see the test
+    51: [(0, 0), (1, 1), (2, 2), (3, 1), (-1, 1)],
+}
+OPTION_EDGES.update({key: [(-1, 1), (7, 1), (0, 0), (1, 1)] for key in OPTION_FLAGS})
+OPTION_EDGES.update({key: [(-5, 0), (0, 0), (17, 17), (1 << 40, 1 << 40)]
+                     for key in OPTION_AT_LEAST_0})
+OPTION_EDGES.update({key: [(lo - 1, lo), (lo - 100, lo), (lo, lo), ((lo + hi) // 2, (lo + hi) // 2),
+                           (hi, hi), (hi + 1, hi), (hi + 10 ** 6, hi)]
+                     for key, (lo, hi) in OPTION_CLAMPS.items()})
+OPTION_EDGES[40] += [(5, 10), (2000000, 1000000)]
+OPTION_EDGES[44] += [(-5, -1), (100, 64)]
+OPTION_READ_ONLY = [6, 10, 12, 16, 24, 25, 42, 43]
+OPTION_TUNE_BUILD_ONLY = 47  # exists only in the -DRSE_TUNE_SPLITS build (make tune)
+
+
+def test_option_defaults_edges_and_read_only_keys():
+    """All 44 settable keys start at their defaults (fresh process), store
+    what their rule makes of a value below, inside and above the range, and
+    the read-only counters and unknown keys refuse a set with one code."""
+    defaults = {key: v for v, keys in OPTION_DEFAULTS.items() for key in keys}
+    assert len(defaults) == 44 and sorted(defaults) == sorted(OPTION_EDGES)
+    assert not set(defaults) & set(OPTION_READ_ONLY + [OPTION_TUNE_BUILD_ONLY, 99])
+    out = _py(PRELUDE + f"print(*[L.rse_get_option(k) for k in {sorted(defaults)}])",
+              dict(os.environ, RSE_TUNE="1"))
+    assert out.returncode == 0, out.stderr[-2000:]
+    assert [int(v) for v in out.stdout.split()] == [defaults[key] for key in sorted(defaults)]
+
+    INVALID_ARGUMENT = L.rse_set_option(99, 1)
+    assert INVALID_ARGUMENT != 0 and L.rse_get_option(99) == -1
+    tune_build = L.rse_get_option(OPTION_TUNE_BUILD_ONLY) != -1
+    for key in OPTION_READ_ONLY + ([] if tune_build else [OPTION_TUNE_BUILD_ONLY]):
+        before = L.rse_get_option(key)
+        assert L.rse_set_option(key, 1) == INVALID_ARGUMENT, key
+        assert L.rse_get_option(key) == before, key
+
+    old = {key: L.rse_get_option(key) for key in defaults}
+    try:
+        for key, cases in OPTION_EDGES.items():
+            for value, want in cases:
+                assert L.rse_set_option(key, value) == 0, (key, value)
+                assert L.rse_get_option(key) == want, (key, value)
+        if not tune_build:  # the wrong-byte timing splits: refused, the setting kept
+            for kept in (0, 8):
+                assert L.rse_set_option(28, kept) == 0
+                for bad in (4, 5):
+                    assert L.rse_set_option(28, bad) == INVALID_ARGUMENT
+                    assert L.rse_get_option(28) == kept
+    finally:
+        for key, v in old.items():
+            L.rse_set_option(key, v)
+    assert {key: L.rse_get_option(key) for key in defaults} == old
+
+
 def test_now_entries_validate_like_the_stream_entries():
     """rse_encode_now / rse_verify_now / rse_reconstruct(_data)_now (the
     synchronous forms, core.rs:597-695's contract) return the same errors as
