@@ -247,6 +247,47 @@ int rse_correct_flat(const rse_codec *codec, void *stripes, size_t shard_len, si
                      uint8_t *changed,       /* nullable, n_stripes x (k+p) */
                      uint32_t *counts,       /* nullable, n_stripes x 2 */
                      rse_stream_t stream);
+/* Scrub: rse_correct_flat at the speed of rse_verify_flat where the stripes
+ * are clean, and the list of those that were not.  `stripes`, `present`,
+ * `status`, `changed` and `counts` are rse_correct_flat's, word for word: every
+ * byte column decoded on its own, erasures beside errors with 2 nu + f <= p per
+ * column, a stripe with f > p neither read nor written, saturating counts.  For
+ * a codec both entries accept, those outputs and the stripe bytes after the
+ * call equal rse_correct_flat's on the same input.
+ *   n_bad        n_bad[0] = the number of stripes whose status is not
+ *                RSE_CORRECT_CLEAN;
+ *   bad_stripes  their indices in ascending order in bad_stripes[0 .. n_bad);
+ *                entries from n_bad on are not written.
+ * Either may be NULL alone.  All pointers but `codec` are device memory.
+ * Codecs: rse_locate_flat's, and GF(2^16) codecs with 1 <= p <= 16 and
+ * k + p <= 255 (their coefficients lie in the GF(2^8) subfield, so each byte of
+ * each element is a GF(2^8) codeword of the same matrix; whatever
+ * RSE_OPT_SUBFIELD says).  For those `shard_len` counts elements as everywhere
+ * in this header, the decoder runs over 2 x shard_len bytes per shard, a byte
+ * column is a column of bytes and counts[s][0] counts bytes.
+ * Where the check of rse_verify_flat runs on bit-sliced or FFT kernels
+ * (rse_codec_kernel_kind COMPILED, SPECIALISED or FFT; shards of 1 KiB, 2 KiB
+ * or at least 4 KiB, 16-byte aligned) it runs first with its verdicts kept on
+ * the device, and the repair pass visits only the stripes that failed it or
+ * have an erased flag; otherwise the repair pass visits every stripe.  A codec
+ * whose kernels are still being specialised is never waited for.
+ * rse_last_kernel() names the route: "scrub gf8 10+4 prefilter" / "... direct".
+ * Asynchronous on `stream`, no host synchronisation; every workspace is a
+ * stream-ordered allocation of the call, so concurrent calls on different
+ * streams share nothing.
+ * Validation, before any device call, in this order: NULL codec / stripes /
+ * status -> RSE_ERR_INVALID_ARGUMENT; a codec out of scope ->
+ * RSE_ERR_INVALID_ARGUMENT; shard_len == 0 -> RSE_EMPTY_SHARD; n_stripes == 0
+ * -> RSE_OK, nothing touched (n_bad neither); n_stripes > 2^32 - 1 ->
+ * RSE_ERR_INVALID_ARGUMENT. */
+int rse_scrub_flat(const rse_codec *codec, void *stripes, size_t shard_len, size_t n_stripes,
+                   const uint8_t *present, /* nullable, n_stripes x (k+p) */
+                   uint8_t *status,        /* n_stripes: RSE_CORRECT_* */
+                   uint8_t *changed,       /* nullable, n_stripes x (k+p) */
+                   uint32_t *counts,       /* nullable, n_stripes x 2 */
+                   uint32_t *bad_stripes,  /* nullable, n_stripes */
+                   uint32_t *n_bad,        /* nullable, 1 */
+                   rse_stream_t stream);
 /* Same layout; every stripe has the same erasure pattern `present[k+p]`
  * (wasm reconstruct(): reconstruct_data semantics). */
 int rse_reconstruct_data_flat(const rse_codec *codec, void *stripes, size_t shard_len,

@@ -134,5 +134,11 @@
                                          launched = this x the workgroups the device holds at once
                                          (the kernel's occupancy x compute units); 1..16, default 1.
                                          RSE_OPT_GRID_X > 0 still sets the count outright */
+#define RSE_OPT_SCRUB_ROUTE 56        /* rse_scrub_flat: 1 (default) the check pass of
+                                         rse_verify_flat first and the repair over the stripes it
+                                         failed, when that check runs on bit-sliced or FFT kernels
+                                         now, else the repair pass over every stripe; 0: always
+                                         the repair pass over every stripe (direct); 2: always the
+                                         check first (pre-filter).  Same results (tests, A/B) */
 
 #endif /* RSE_HIP_TUNE_H */

@@ -833,6 +833,31 @@ void want_bitslice(const rse_codec* c, size_t len_bytes, bool now = false, size_
     rse::jit_register(c->kfield, (uint32_t)c->k, (uint32_t)c->p, rows.c.data(), rse::kJitCodec);
 }
 
+// rse_codec_kernel_kind with the codec's parity rows at hand (a caller that
+// needs them anyway makes them once).
+int kernel_kind_of(const rse_codec* c, const Rows& rows, int wait) {
+  if (rse::bitslice_compiled(c->kfield, (uint32_t)c->k, (uint32_t)c->p)) return RSE_KERNELS_COMPILED;
+  if (rse::fft_applies(c->kfield, (uint32_t)c->k, (uint32_t)c->p, rows.c.data()))
+    return RSE_KERNELS_FFT;
+  if (rse::fft16_applies(c->kfield, (uint32_t)c->k, (uint32_t)c->p, rows.c.data()))
+    return RSE_KERNELS_FFT;
+  if (wait) want_bitslice(c, rse::bitslice_chunk_bytes(), true);
+  const bool wide = c->k > (size_t)kMaxIn || c->p > rse::kJitMaxOut ||
+                    rse::wide_eligible((uint32_t)c->k, (uint32_t)c->p);
+  const bool one = rse::wide_eligible((uint32_t)c->k, (uint32_t)c->p);
+  switch (wide ? (one ? rse::jit_wide_status(c->kfield, (uint32_t)c->k, (uint32_t)c->p,
+                                             rows.c.data(), wait != 0)
+                      : rse::jit_blocks_status(c->kfield, (uint32_t)c->k, (uint32_t)c->p,
+                                               rows.c.data(), wait != 0))
+               : rse::jit_status(c->kfield, (uint32_t)c->k, (uint32_t)c->p, rows.c.data(),
+                                 wait != 0)) {
+    case 2: return RSE_KERNELS_SPECIALISED;
+    case 1: return RSE_KERNELS_SPECIALISING;
+    case -1: return RSE_KERNELS_SPECIALISE_FAILED;
+    default: return RSE_KERNELS_TABLE;
+  }
+}
+
 Rows single_column(const rse_codec* c, size_t i_data) {  // code_single_slice, core.rs:492-509
   Rows r;
   r.n_out = c->p;
@@ -1903,26 +1928,7 @@ size_t rse_codec_total_shard_count(const rse_codec* c) { return c ? c->total : 0
 int rse_codec_kernel_kind(const rse_codec* c, int wait) {
   if (!c) return RSE_ERR_INVALID_ARGUMENT;
   if (rse::bitslice_compiled(c->kfield, (uint32_t)c->k, (uint32_t)c->p)) return RSE_KERNELS_COMPILED;
-  const Rows rows = parity_rows(c);
-  if (rse::fft_applies(c->kfield, (uint32_t)c->k, (uint32_t)c->p, rows.c.data()))
-    return RSE_KERNELS_FFT;
-  if (rse::fft16_applies(c->kfield, (uint32_t)c->k, (uint32_t)c->p, rows.c.data()))
-    return RSE_KERNELS_FFT;
-  if (wait) want_bitslice(c, rse::bitslice_chunk_bytes(), true);
-  const bool wide = c->k > (size_t)kMaxIn || c->p > rse::kJitMaxOut ||
-                    rse::wide_eligible((uint32_t)c->k, (uint32_t)c->p);
-  const bool one = rse::wide_eligible((uint32_t)c->k, (uint32_t)c->p);
-  switch (wide ? (one ? rse::jit_wide_status(c->kfield, (uint32_t)c->k, (uint32_t)c->p,
-                                             rows.c.data(), wait != 0)
-                      : rse::jit_blocks_status(c->kfield, (uint32_t)c->k, (uint32_t)c->p,
-                                               rows.c.data(), wait != 0))
-               : rse::jit_status(c->kfield, (uint32_t)c->k, (uint32_t)c->p, rows.c.data(),
-                                 wait != 0)) {
-    case 2: return RSE_KERNELS_SPECIALISED;
-    case 1: return RSE_KERNELS_SPECIALISING;
-    case -1: return RSE_KERNELS_SPECIALISE_FAILED;
-    default: return RSE_KERNELS_TABLE;
-  }
+  return kernel_kind_of(c, parity_rows(c), wait);
 }
 
 int rse_codec_matrix(const rse_codec* c, uint8_t* out, size_t out_bytes) {
@@ -2088,18 +2094,15 @@ int run_now(const rse_codec* c, const Rows& rows, const uint8_t* const* in, uint
   return RSE_OK;
 }
 
-// What rse_locate_flat and rse_correct_flat (`what`) do around their kernels,
-// after their own null checks.  Validation first: it touches no device, so the
-// stream's device is made current only after it.  Then the codec's plan there
-// (copied to the device once, on the first call), the per-stripe accumulators
-// in a stream-ordered workspace, launch(args, stream), and the workspace's
-// free.  No host synchronisation.
+// What the locating entries do around their kernels once the call is
+// validated: the stream's device made current, the codec's plan there (copied
+// to the device once, on the first call), the per-stripe accumulators in a
+// stream-ordered workspace with `extra_words` 32-bit words after them,
+// launch(args, stream) -- an RSE code -- and the workspace's free.  No host
+// synchronisation.  shard_bytes: of a shard, as the GF(2^8) decoder sees it.
 template <class Launch>
-int locate_pass(const rse_codec* c, const void* stripes, size_t shard_len, size_t n_stripes,
-                rse_stream_t stream, const char* what, const Launch& launch) {
-  if (!rse::locate_in_scope(c->field, c->k, c->p)) return RSE_ERR_INVALID_ARGUMENT;
-  if (shard_len == 0) return RSE_EMPTY_SHARD;
-  if (n_stripes == 0) return RSE_OK;
+int locate_run(const rse_codec* c, const void* stripes, size_t shard_bytes, size_t n_stripes,
+               size_t extra_words, rse_stream_t stream, const Launch& launch) {
   RSE_ON_STREAM(stream);
   hipStream_t st = (hipStream_t)stream;
   int dev = 0;
@@ -2107,18 +2110,55 @@ int locate_pass(const rse_codec* c, const void* stripes, size_t shard_len, size_
   rse::LocateArgs a{};
   RSE_HIP(locate_plan_consts(c, dev, &a.consts));
   RSE_HIP(hipMallocAsync(reinterpret_cast<void**>(&a.acc),
-                         n_stripes * rse::kLocAccWords * sizeof(uint32_t), st));
+                         (n_stripes * rse::kLocAccWords + extra_words) * sizeof(uint32_t), st));
   a.base = static_cast<const uint8_t*>(stripes);
-  a.shard_bytes = shard_len;
+  a.shard_bytes = shard_bytes;
   a.n_stripes = n_stripes;
   a.k = (uint32_t)c->k;
   a.p = (uint32_t)c->p;
-  const hipError_t e = launch(a, st);
+  const int rc = launch(a, st);
   const hipError_t f = hipFreeAsync(a.acc, st);
-  if (e != hipSuccess) return dev_fail(e);
+  if (rc != RSE_OK) return rc;
   if (f != hipSuccess) return dev_fail(f);
-  rse::note_kernel("%s gf8 %zu+%zu", what, c->k, c->p);
   return RSE_OK;
+}
+
+// What rse_locate_flat and rse_correct_flat (`what`) do after their own null
+// checks.  Validation first: it touches no device, so the stream's device is
+// made current only after it (locate_run).
+template <class Launch>
+int locate_pass(const rse_codec* c, const void* stripes, size_t shard_len, size_t n_stripes,
+                rse_stream_t stream, const char* what, const Launch& launch) {
+  if (!rse::locate_in_scope(c->field, c->k, c->p)) return RSE_ERR_INVALID_ARGUMENT;
+  if (shard_len == 0) return RSE_EMPTY_SHARD;
+  if (n_stripes == 0) return RSE_OK;
+  const int rc = locate_run(c, stripes, shard_len, n_stripes, 0, stream,
+                            [&](const rse::LocateArgs& a, hipStream_t st) {
+                              const hipError_t e = launch(a, st);
+                              return e == hipSuccess ? RSE_OK : dev_fail(e);
+                            });
+  if (rc == RSE_OK) rse::note_kernel("%s gf8 %zu+%zu", what, c->k, c->p);
+  return rc;
+}
+
+// Which route rse_scrub_flat takes over `shard_bytes` of every shard (DESIGN
+// §4.L3): true, pre-filter -- the check pass of rse_verify_flat first, the
+// repair over the stripes it failed -- when that check runs on bit-sliced or
+// FFT kernels now: kernels of the codec's own that exist (a module still
+// building is not waited for, and a wide codec never pays its table check),
+// and a shard length and alignment they take (run_job).  False, direct: the
+// repair pass over every stripe.  RSE_OPT_SCRUB_ROUTE 0 / 2 force either.
+// rows: the codec's parity rows.
+bool scrub_prefilters(const rse_codec* c, const Rows& rows, const void* stripes,
+                      size_t shard_bytes) {
+  const int64_t route = rse::get_option(RSE_OPT_SCRUB_ROUTE);
+  if (route != 1) return route == 2;
+  if (!bitslice_len(shard_bytes) || shard_bytes % 16u != 0 || !aligned16(stripes) ||
+      !rse::get_option(RSE_OPT_BITSLICE))
+    return false;
+  const int kind = kernel_kind_of(c, rows, 0);
+  return kind == RSE_KERNELS_COMPILED || kind == RSE_KERNELS_SPECIALISED ||
+         kind == RSE_KERNELS_FFT;
 }
 
 }  // namespace
@@ -2247,6 +2287,66 @@ int rse_correct_flat(const rse_codec* c, void* stripes, size_t shard_len, size_t
                        return rse::launch_correct(rse::CorrectArgs{a, present}, status, changed,
                                                   counts, st);
                      });
+}
+
+// rse_correct_flat's results, and the list of the stripes that did not end
+// CLEAN, by one of two routes (scrub_prefilters).  Pre-filter: the verdict
+// words zeroed, rse_verify_flat's job with the words kept on the device, the
+// work list compacted from them (and from the erased flags), the repair over
+// that list.  Without `present` the work list is the caller's list -- a stripe
+// that fails the check has a column that is stored or left undecodable -- so
+// it is compacted straight into the caller's arrays; with `present` it can
+// hold stripes that end CLEAN, and the caller's list is compacted from
+// `status`, as on the direct route.  A GF(2^16) codec is decoded byte by byte
+// (its coefficients lie in the GF(2^8) subfield: rse_codec::kfield), the check
+// pass in the codec's own kfield.
+int rse_scrub_flat(const rse_codec* c, void* stripes, size_t shard_len, size_t n_stripes,
+                   const uint8_t* present, uint8_t* status, uint8_t* changed, uint32_t* counts,
+                   uint32_t* bad_stripes, uint32_t* n_bad, rse_stream_t stream) {
+  if (!c || !stripes || !status) return RSE_ERR_INVALID_ARGUMENT;
+  if (!rse::locate_in_scope(RSE_FIELD_GF8, c->k, c->p)) return RSE_ERR_INVALID_ARGUMENT;
+  if (shard_len == 0) return RSE_EMPTY_SHARD;
+  if (n_stripes == 0) return RSE_OK;
+  if (n_stripes > 0xffffffffu) return RSE_ERR_INVALID_ARGUMENT;
+  const size_t sb = shard_len * c->esize();
+  // as rse_verify_flat: a codec without kernels of its own has them requested
+  // (never waited for), so that a process that only scrubs reaches the
+  // pre-filter route too
+  want_bitslice(c, sb, false, n_stripes);
+  const Rows rows = parity_rows(c);
+  const bool pre = scrub_prefilters(c, rows, stripes, sb);
+  const uint32_t n = (uint32_t)c->total;
+  const int rc = locate_run(
+      c, stripes, sb, n_stripes, pre ? 2 * n_stripes + 1 : 0, stream,
+      [&](const rse::LocateArgs& a, hipStream_t st) {
+        const rse::CorrectArgs ca{a, present};
+        bool listed = false;  // the caller's list is written already
+        if (pre) {
+          uint32_t* words = a.acc + n_stripes * rse::kLocAccWords;
+          listed = present == nullptr;
+          uint32_t* list = listed && bad_stripes ? bad_stripes : words + n_stripes;
+          uint32_t* count = listed && n_bad ? n_bad : words + 2 * n_stripes;
+          RSE_HIP(hipMemsetAsync(words, 0, n_stripes * sizeof(uint32_t), st));
+          const uint8_t* base = static_cast<const uint8_t*>(stripes);
+          std::vector<const uint8_t*> in(c->k), cmp(c->p);
+          for (size_t i = 0; i < c->k; ++i) in[i] = base + i * sb;
+          for (size_t r = 0; r < c->p; ++r) cmp[r] = base + (c->k + r) * sb;
+          Job j{c->kfield, &rows, in.data(), nullptr, cmp.data(), sb, rse::kCheck, false, words,
+                (uint64_t)n * sb, n_stripes, true};
+          if (const int jr = run_job(j, st)) return jr;
+          RSE_HIP(rse::launch_scrub_compact(words, present, n, nullptr, n_stripes, list, count, st));
+          RSE_HIP(rse::launch_correct_list(ca, list, count, status, changed, counts, st));
+        } else {
+          RSE_HIP(rse::launch_correct(ca, status, changed, counts, st));
+        }
+        if (!listed && (bad_stripes || n_bad))
+          RSE_HIP(rse::launch_scrub_compact(nullptr, nullptr, n, status, n_stripes, bad_stripes,
+                                            n_bad, st));
+        return (int)RSE_OK;
+      });
+  if (rc == RSE_OK)
+    rse::note_kernel("scrub gf%d %zu+%zu %s", c->field, c->k, c->p, pre ? "prefilter" : "direct");
+  return rc;
 }
 
 int rse_reconstruct_data_flat(const rse_codec* c, void* stripes, size_t shard_len,

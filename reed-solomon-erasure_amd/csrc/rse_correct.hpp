@@ -25,4 +25,20 @@ struct CorrectArgs {
 hipError_t launch_correct(const CorrectArgs& a, uint8_t* status, uint8_t* changed,
                           uint32_t* counts, hipStream_t stream);
 
+// rse_scrub_flat's pre-filter route.  The same two passes, the first over the
+// stripes list[0 .. *n_list) only (both device memory, read on the device; the
+// list's stripes are distinct and below a.loc.n_stripes): every other stripe
+// comes out CLEAN with nothing changed.
+hipError_t launch_correct_list(const CorrectArgs& a, const uint32_t* list, const uint32_t* n_list,
+                               uint8_t* status, uint8_t* changed, uint32_t* counts,
+                               hipStream_t stream);
+
+// Ascending into list[0 .. *count): the stripes with a nonzero word in `words`
+// (n_stripes), a zero flag in their row of `present` (n_stripes x n) or a
+// nonzero `status` (n_stripes); each of the three, and list and count, may be
+// null.  Entries from *count on are not written.  n_stripes < 2^32.
+hipError_t launch_scrub_compact(const uint32_t* words, const uint8_t* present, uint32_t n,
+                                const uint8_t* status, uint64_t n_stripes, uint32_t* list,
+                                uint32_t* count, hipStream_t stream);
+
 }  // namespace rse

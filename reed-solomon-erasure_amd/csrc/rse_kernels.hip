@@ -861,11 +861,12 @@ constexpr OptionRow kOptionRows[] = {
     {RSE_OPT_HOST_ZC_OUT, 1, flag()},  // host pipeline: outputs stored in place in mapped pinned memory
     {RSE_OPT_FFT16, 0, flag()},  // GF(2^16) codecs past 256 shards with 2^m - k <= 32 on the pruned-FFT kernel (rse_fft16.hip)
     {RSE_OPT_TICKET_GRID, 1, clamp(1, 16)},  // ticket kernels (rse_bitslice_ticket.hpp): workgroups = this x resident
+    {RSE_OPT_SCRUB_ROUTE, 1, clamp(0, 2)},  // rse_scrub_flat: 0 direct, 1 by the rule (rse_codec.cpp scrub_prefilters), 2 pre-filter
 };
 
 // The rows by key, and every key's value: -1, get_option's answer for a key
 // that does not exist, where there is no row.
-constexpr int kOptionKeys = 56;
+constexpr int kOptionKeys = 57;
 struct OptionTable {
   OptionRow row[kOptionKeys] = {};
   std::array<int64_t, kOptionKeys> def = {};

@@ -137,15 +137,31 @@ __device__ __forceinline__ void loc_unit(const LocateArgs& a, uint4* tq, uint32_
   if (any != 0u) slow(acc, sbase, off);
 }
 
+// Units of 256 lanes in a stripe's sweep: the 16-byte vectors, then the
+// byte-wise part.
+__device__ __forceinline__ uint64_t loc_units(const LocateArgs& a) {
+  return (a.n_vec + kLocBlock - 1) / kLocBlock +
+         (a.shard_bytes - a.n_vec * 16u + kLocBlock - 1) / kLocBlock;
+}
+
+// Which of a stripe's units a workgroup takes: it is number first() of the
+// step() workgroups that share the stripe.  Here for a grid of (workgroups per
+// stripe) x (stripes in flight), loc_grid's.
+struct LocGridPart {
+  __device__ __forceinline__ uint32_t first() const { return blockIdx.x; }
+  __device__ __forceinline__ uint32_t step() const { return gridDim.x; }
+};
+
 // The sweep of one stripe by one workgroup: its units of 256 lanes, 16-byte
 // vectors first, then the byte-wise part.
-template <int NO, bool MULTI, class Slow>
+template <int NO, bool MULTI, class Slow, class Part = LocGridPart>
 __device__ __forceinline__ void loc_sweep(const LocateArgs& a, uint4* tq, uint32_t* tt2,
-                                          const uint8_t* sbase, const Slow& slow) {
+                                          const uint8_t* sbase, const Slow& slow,
+                                          const Part& part = Part{}) {
   const uint64_t n_vspans = (a.n_vec + kLocBlock - 1) / kLocBlock;
   const uint64_t tail0 = a.n_vec * 16u;  // first byte of the byte-wise part
   const uint64_t n_units = n_vspans + (a.shard_bytes - tail0 + kLocBlock - 1) / kLocBlock;
-  for (uint64_t u = blockIdx.x; u < n_units; u += gridDim.x) {
+  for (uint64_t u = part.first(); u < n_units; u += part.step()) {
     if (u < n_vspans) {
       const uint64_t v = u * kLocBlock + threadIdx.x;
       loc_unit<NO, 4, MULTI>(a, tq, tt2, sbase, v * 16u, v < a.n_vec, slow);

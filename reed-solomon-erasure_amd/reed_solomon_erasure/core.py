@@ -93,6 +93,23 @@ def _check_flat(stripes: torch.Tensor, shard_len: int, n_stripes: int, total: in
         raise ValueError(f"stripes holds {stripes.numel()} bytes, {need} needed")
 
 
+def _stripe_flags(present, stripes: torch.Tensor, n_stripes: int, total: int):
+    """correct_flat()'s / scrub_flat()'s per-stripe flags on the stripes' device
+    (None stays None): a device tensor is read in place, a host array uploaded."""
+    if present is None:
+        return None
+    if isinstance(present, torch.Tensor) and present.is_cuda:
+        pres = present  # read in place, on that device
+    else:
+        flags = np.ascontiguousarray(np.asarray(
+            present.cpu() if isinstance(present, torch.Tensor) else present, dtype=bool))
+        pres = torch.from_numpy(flags.view(np.uint8)).to(stripes.device)
+    if (tuple(pres.shape) != (n_stripes, total) or not pres.is_contiguous()
+            or pres.dtype not in (torch.bool, torch.uint8) or pres.device != stripes.device):
+        raise RSError(Error.InvalidShardFlags)
+    return pres
+
+
 _U8 = torch.uint8
 
 
@@ -396,18 +413,7 @@ class ReedSolomon:
         T = self.total_shard_count()
         _check_flat(stripes, shard_len, n_stripes, T, self.field)
         base = _dev(stripes)
-        pres = None
-        if present is not None:
-            if isinstance(present, torch.Tensor) and present.is_cuda:
-                pres = present  # read in place, on that device
-            else:
-                flags = np.ascontiguousarray(np.asarray(
-                    present.cpu() if isinstance(present, torch.Tensor) else present, dtype=bool))
-                pres = torch.from_numpy(flags.view(np.uint8)).to(stripes.device)
-            if (tuple(pres.shape) != (n_stripes, T) or not pres.is_contiguous()
-                    or pres.dtype not in (torch.bool, torch.uint8)
-                    or pres.device != stripes.device):
-                raise RSError(Error.InvalidShardFlags)
+        pres = _stripe_flags(present, stripes, n_stripes, T)
         # at least one row: an empty tensor has no address to pass
         rows = max(1, n_stripes)
         status = torch.empty((rows,), dtype=torch.uint8, device=stripes.device)
@@ -418,6 +424,38 @@ class ReedSolomon:
                                      status.data_ptr(), changed.data_ptr(), counts.data_ptr(),
                                      _stream(stripes)))
         return status[:n_stripes], changed[:n_stripes], counts[:n_stripes]
+
+    def scrub_flat(self, stripes: torch.Tensor, shard_len: int, n_stripes: int = 1, present=None
+                   ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+        """Scrub every stripe of the flat layout in place (rse_scrub_flat):
+        correct_flat()'s repair and ``(status, changed, counts)``, at the speed
+        of the verify kernels where the stripes are clean, and with them
+        ``(bad_stripes, n_bad)``: int32 device tensors of shapes
+        ``(n_stripes,)`` and ``(1,)``.  ``n_bad[0]`` is the number of stripes
+        whose status is not CORRECT_CLEAN and ``bad_stripes[:n_bad]`` their
+        indices in ascending order; the entries past them are not written.
+        ``present`` as in correct_flat().  Queued on the current stream, no
+        synchronisation: ``n_bad`` is read by whoever needs the count, after
+        synchronising.  Codecs of locate_flat(), and galois_16 codecs with
+        p <= 16 and k + p <= 255, which are decoded byte by byte (``counts``
+        then counts bytes and byte columns)."""
+        T = self.total_shard_count()
+        _check_flat(stripes, shard_len, n_stripes, T, self.field)
+        base = _dev(stripes)
+        pres = _stripe_flags(present, stripes, n_stripes, T)
+        # at least one row: an empty tensor has no address to pass
+        rows = max(1, n_stripes)
+        status = torch.empty((rows,), dtype=torch.uint8, device=stripes.device)
+        changed = torch.empty((rows, T), dtype=torch.uint8, device=stripes.device)
+        counts = torch.empty((rows, 2), dtype=torch.int32, device=stripes.device)
+        bad_stripes = torch.empty((rows,), dtype=torch.int32, device=stripes.device)
+        n_bad = torch.zeros((1,), dtype=torch.int32, device=stripes.device)
+        _raise(_lib.rse_scrub_flat(self._h, base, shard_len, n_stripes,
+                                   pres.data_ptr() if pres is not None and n_stripes else None,
+                                   status.data_ptr(), changed.data_ptr(), counts.data_ptr(),
+                                   bad_stripes.data_ptr(), n_bad.data_ptr(), _stream(stripes)))
+        return (status[:n_stripes], changed[:n_stripes], counts[:n_stripes],
+                bad_stripes[:n_stripes], n_bad)
 
     def reconstruct_data_flat(self, stripes: torch.Tensor, shard_len: int, n_stripes: int,
                               present: Sequence[bool]) -> None:
