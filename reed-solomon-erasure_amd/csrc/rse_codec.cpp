@@ -772,10 +772,12 @@ Rows rows_from_bytes(int field, const uint8_t* rows, size_t n_out, size_t n_in) 
 // Byte offset of the planner tables in a codec's plan constants.
 size_t plan_tab_off(const rse_codec* c) { return (c->p * c->k * 2 + 255) & ~size_t(255); }
 
-// The codec's plan constants on device `dev` (rse_codec::plan_dev; the first
+// The codec's plan constants on the current device (rse_codec::plan_dev; the first
 // batched reconstruct there pays the copy).
-hipError_t plan_consts(const rse_codec* c, int dev, const uint8_t** out) {
-  return c->plan_dev.get(dev, [c] {
+hipError_t plan_consts(const rse_codec* c, const uint8_t** out) {
+  int dev = 0;
+  const hipError_t e = hipGetDevice(&dev);
+  return e != hipSuccess ? e : c->plan_dev.get(dev, [c] {
     const Rows r = parity_rows(c);
     const size_t off = plan_tab_off(c);
     std::vector<uint8_t> h(off + rse::kPlanTabBytes, 0);
@@ -1468,6 +1470,57 @@ struct HostCode {
   bool any_mem = false;
 };
 
+// One host op as both host paths see it, computed once from (c, op, code):
+// the field and the shard counts (codec ops: the codec's; kCode: those of the
+// caller's rows), the shards of one device set, and the rows to code.
+struct HostShape {
+  const rse_codec* c;
+  HostOp op;
+  bool low, verify, accumulate, any_mem;
+  int field;
+  size_t k, T, p, es, nbuf;  // nbuf: shards per device set (kVerifyBuf: + p buffer shards)
+  Rows parity;               // codec ops: the codec's parity rows
+  const Rows* given;         // kCode: the caller's rows
+  const Rows& rows() const { return low ? *given : parity; }
+  HostShape(const rse_codec* c_, HostOp op_, const HostCode* code)
+      : c(c_), op(op_), low(op_ == HostOp::kCode),
+        verify(op_ == HostOp::kVerify || op_ == HostOp::kVerifyBuf),
+        accumulate(low && code->accumulate), any_mem(low && code->any_mem),
+        field(low ? code->field : c_->field), k(low ? code->rows->n_in : c_->k),
+        T(low ? k + code->rows->n_out : c_->total), p(T - k),
+        es(field == RSE_FIELD_GF16 ? 2 : 1), nbuf(T + (op_ == HostOp::kVerifyBuf ? p : 0)),
+        parity(low ? Rows{} : parity_rows(c_)), given(low ? code->rows : nullptr) {}
+};
+
+// Runs the op over `bytes` of every shard of one device set (dev[i]: shard i,
+// dev[T + r]: buffer shard r) on `s`.  present: kRecon*, the stripe's flags;
+// mismatch: verify ops, the device word a differing byte sets.
+int run_host_op(const HostShape& h, uint8_t* const* dev, size_t bytes, const uint8_t* present,
+                uint32_t* mismatch, hipStream_t s) {
+  switch (h.op) {
+    case HostOp::kEncode:
+    case HostOp::kCode: {
+      Job j{h.field, &h.rows(), dev, dev + h.k, nullptr, bytes, rse::kStore, h.accumulate, nullptr,
+            0, 1};
+      return run_job(j, s);
+    }
+    case HostOp::kVerify:
+    case HostOp::kVerifyBuf: {
+      const bool wb = h.op == HostOp::kVerifyBuf;
+      Job j{h.field, &h.rows(), dev, wb ? dev + h.T : nullptr, dev + h.k, bytes,
+            wb ? rse::kCheckStore : rse::kCheck, false, mismatch, 0, 1};
+      return run_job(j, s);
+    }
+    case HostOp::kRecon:
+    case HostOp::kReconData: {
+      const std::vector<size_t> lens(h.T, bytes / h.es);
+      return reconstruct_impl(h.c, reinterpret_cast<void* const*>(dev), lens.data(), present, h.T,
+                              h.op == HostOp::kReconData, s);
+    }
+  }
+  return RSE_ERR_INVALID_ARGUMENT;
+}
+
 // Small calls: one stripe moving at most kHostDirectBytes (both ways) skips
 // the pipeline.  Its per-shard copies cost ~10 us of runtime work each for
 // pageable memory (the runtime stages every one), ~170 us for a 10+4 stripe
@@ -1478,20 +1531,14 @@ struct HostCode {
 // copies them out.
 constexpr size_t kHostDirectBytes = size_t(2) << 20;
 
-int host_direct(const rse_codec* c, HostOp op, const HostStripe& hs, size_t bytes, hipStream_t user,
-                int* ok, const HostCode* code, bool* handled) {
+int host_direct(const HostShape& h, const HostStripe& hs, size_t bytes, hipStream_t user, int* ok,
+                bool* handled) {
   *handled = false;
-  const bool low = op == HostOp::kCode;
-  if (low && code->any_mem) return RSE_OK;  // device memory among the buffers: the pipeline
-  const bool verify = op == HostOp::kVerify || op == HostOp::kVerifyBuf;
-  const int field = low ? code->field : c->field;
-  const size_t k = low ? code->rows->n_in : c->k;
-  const size_t T = low ? k + code->rows->n_out : c->total;
-  const size_t p = T - k, es = field == RSE_FIELD_GF16 ? 2 : 1;
-  const size_t nbuf = T + (op == HostOp::kVerifyBuf ? p : 0);
+  if (h.any_mem) return RSE_OK;  // device memory among the buffers: the pipeline
+  const bool verify = h.verify;
+  const size_t T = h.T, nbuf = h.nbuf;
   std::vector<uint32_t> up, down;
-  host_sets((uint32_t)k, (uint32_t)T, (uint32_t)p, op, low && code->accumulate, hs.present, up,
-            down);
+  host_sets((uint32_t)h.k, (uint32_t)T, (uint32_t)h.p, h.op, h.accumulate, hs.present, up, down);
   if ((up.size() + down.size()) * bytes > kHostDirectBytes) return RSE_OK;
   *handled = true;
   if (down.empty() && !verify) return RSE_OK;  // nothing to rebuild
@@ -1519,32 +1566,7 @@ int host_direct(const rse_codec* c, HostOp op, const HostStripe& hs, size_t byte
   }
   std::vector<uint8_t*> dev(nbuf);
   for (size_t i = 0; i < nbuf; ++i) dev[i] = dbuf + i * sz;
-  const Rows rows = low ? Rows{} : parity_rows(c);
-  const Rows& code_rows = low ? *code->rows : rows;
-  std::vector<size_t> lens(T, bytes / es);
-  int rc = RSE_OK;
-  switch (op) {
-    case HostOp::kEncode:
-    case HostOp::kCode: {
-      Job j{field, &code_rows, dev.data(), dev.data() + k, nullptr, bytes, rse::kStore,
-            low && code->accumulate, nullptr, 0, 1};
-      rc = run_job(j, user);
-      break;
-    }
-    case HostOp::kVerify:
-    case HostOp::kVerifyBuf: {
-      const bool wb = op == HostOp::kVerifyBuf;
-      Job j{field, &rows, dev.data(), wb ? dev.data() + T : nullptr, dev.data() + k, bytes,
-            wb ? rse::kCheckStore : rse::kCheck, false, dword, 0, 1};
-      rc = run_job(j, user);
-      break;
-    }
-    case HostOp::kRecon:
-    case HostOp::kReconData:
-      rc = reconstruct_impl(c, reinterpret_cast<void* const*>(dev.data()), lens.data(), hs.present,
-                            T, op == HostOp::kReconData, user);
-      break;
-  }
+  const int rc = run_host_op(h, dev.data(), bytes, hs.present, dword, user);
   const size_t d0 = down.empty() ? 0 : down.front(), d1 = down.empty() ? 0 : down.back() + 1;
   if (rc == RSE_OK && d1 > d0)
     e = hipMemcpyAsync(hst + d0 * sz, dbuf + d0 * sz, (d1 - d0) * sz, hipMemcpyDeviceToHost, user);
@@ -1587,9 +1609,10 @@ uint8_t* mapped_host(const void* p) {
 // its first second of calls and 75 GB/s after (profiles/r06/s9/probe.log).
 int host_pipeline(const rse_codec* c, HostOp op, const std::vector<HostStripe>& stripes,
                   size_t bytes, hipStream_t user, int* ok, const HostCode* code = nullptr) {
+  const HostShape h(c, op, code);
   if (stripes.size() == 1 && rse::get_option(RSE_OPT_HOST_DIRECT)) {
     bool handled = false;
-    const int rc = host_direct(c, op, stripes[0], bytes, user, ok, code, &handled);
+    const int rc = host_direct(h, stripes[0], bytes, user, ok, &handled);
     if (handled || rc) return rc;
   }
   const int64_t chunk_kib = rse::get_option(RSE_OPT_HOST_CHUNK_KIB);
@@ -1598,14 +1621,8 @@ int host_pipeline(const rse_codec* c, HostOp op, const std::vector<HostStripe>& 
   const size_t chunk = std::min<size_t>(bytes, (size_t)std::max<int64_t>(64, chunk_kib) << 10);
   const size_t per_stripe = (bytes + chunk - 1) / chunk;
   const size_t nchunks = per_stripe * stripes.size();
-  const bool verify = op == HostOp::kVerify || op == HostOp::kVerifyBuf;
-  const bool low = op == HostOp::kCode;
-  const bool any_mem = low && code->any_mem;
-  const int field = low ? code->field : c->field;
-  const size_t k = low ? code->rows->n_in : c->k;
-  const size_t T = low ? k + code->rows->n_out : c->total;
-  const size_t p = T - k, es = field == RSE_FIELD_GF16 ? 2 : 1;
-  const size_t nbuf = T + (op == HostOp::kVerifyBuf ? p : 0);  // shards per slot
+  const bool verify = h.verify, any_mem = h.any_mem;
+  const size_t T = h.T, nbuf = h.nbuf;  // nbuf: shards per slot
   // streams: [0, nh) H2D, nh kernel, nh + 1 D2H (leased: Scratch)
   Lease res;
   hipError_t e = res.acquire();
@@ -1632,10 +1649,7 @@ int host_pipeline(const rse_codec* c, HostOp op, const std::vector<HostStripe>& 
   for (auto& q : st)
     if (e == hipSuccess) e = hipStreamWaitEvent(q, start, 0);
   if (op == HostOp::kEncode || verify) want_bitslice(c, chunk);
-  const Rows rows = low ? Rows{} : parity_rows(c);
-  const Rows& code_rows = low ? *code->rows : rows;
   std::vector<uint8_t*> dev(nbuf);
-  std::vector<size_t> lens(T);
   std::vector<uint32_t> up, down;
   hipStream_t kst = st[nh], dst = st[nh + 1];
   int rc = RSE_OK;
@@ -1643,7 +1657,7 @@ int host_pipeline(const rse_codec* c, HostOp op, const std::vector<HostStripe>& 
   // outputs in place: encode / reconstruct, outputs not read (no accumulate)
   const bool zc = rse::get_option(RSE_OPT_HOST_ZC_OUT) &&
                   (op == HostOp::kEncode || op == HostOp::kRecon || op == HostOp::kReconData ||
-                   (low && !code->accumulate && !any_mem));
+                   (h.low && !h.accumulate && !any_mem));
   std::vector<uint8_t*> zmap(nbuf, nullptr);  // the stripe's written shards' device mappings
   bool zc_stripe = false;
   for (size_t ci = 0; e == hipSuccess && rc == RSE_OK && ci < nchunks; ++ci) {
@@ -1653,8 +1667,7 @@ int host_pipeline(const rse_codec* c, HostOp op, const std::vector<HostStripe>& 
       return static_cast<uint8_t*>(i < T ? hs.sh[i] : hs.buf[i - T]);
     };
     if (si != set_for) {
-      host_sets((uint32_t)k, (uint32_t)T, (uint32_t)p, op, low && code->accumulate, hs.present,
-                up, down);
+      host_sets((uint32_t)h.k, (uint32_t)T, (uint32_t)h.p, op, h.accumulate, hs.present, up, down);
       set_for = si;
       zc_stripe = zc && !down.empty();
       for (size_t d = 0; zc_stripe && d < down.size(); ++d) {
@@ -1676,29 +1689,7 @@ int host_pipeline(const rse_codec* c, HostOp op, const std::vector<HostStripe>& 
     for (size_t i = 0; i < nbuf; ++i) dev[i] = set + i * chunk;
     if (zc_stripe)
       for (uint32_t i : down) dev[i] = zmap[i] + off;
-    switch (op) {
-      case HostOp::kEncode:
-      case HostOp::kCode: {
-        Job j{field, &code_rows, dev.data(), dev.data() + k, nullptr, sz, rse::kStore,
-              low && code->accumulate, nullptr, 0, 1};
-        rc = run_job(j, kst);
-        break;
-      }
-      case HostOp::kVerify:
-      case HostOp::kVerifyBuf: {
-        const bool wb = op == HostOp::kVerifyBuf;
-        Job j{field, &rows, dev.data(), wb ? dev.data() + T : nullptr, dev.data() + k, sz,
-              wb ? rse::kCheckStore : rse::kCheck, false, dwords + si, 0, 1};
-        rc = run_job(j, kst);
-        break;
-      }
-      case HostOp::kRecon:
-      case HostOp::kReconData:
-        std::fill(lens.begin(), lens.end(), sz / es);
-        rc = reconstruct_impl(c, reinterpret_cast<void* const*>(dev.data()), lens.data(),
-                              hs.present, T, op == HostOp::kReconData, kst);
-        break;
-    }
+    rc = run_host_op(h, dev.data(), sz, hs.present, dwords + si, kst);
     if (rc) break;
     if (zc_stripe) {  // written in place: the slot is free when the kernel is done
       e = hipEventRecord(d2h[b], kst);
@@ -2161,6 +2152,263 @@ bool scrub_prefilters(const rse_codec* c, const Rows& rows, const void* stripes,
          kind == RSE_KERNELS_FFT;
 }
 
+// The job over n_stripes flat stripes (shard i of stripe s at stripes +
+// (s * total + i) * sb): `rows`, the codec's parity rows, over stripe 0's
+// shards, repeated every total * sb bytes.  kStore writes the parity shards, a
+// check mode compares with them (mismatch, per_stripe: Job).  The job points
+// into `q`, which this fills, and at `rows`: both outlive its run.
+struct FlatPtrs {
+  std::vector<const uint8_t*> in;
+  std::vector<uint8_t*> par;
+};
+Job flat_job(const rse_codec* c, const Rows& rows, const void* stripes, size_t sb, size_t n_stripes,
+             uint32_t mode, uint32_t* mismatch, bool per_stripe, FlatPtrs& q) {
+  uint8_t* base = static_cast<uint8_t*>(const_cast<void*>(stripes));
+  q.in.resize(c->k);
+  q.par.resize(c->p);
+  for (size_t i = 0; i < c->k; ++i) q.in[i] = base + i * sb;
+  for (size_t r = 0; r < c->p; ++r) q.par[r] = base + (c->k + r) * sb;
+  const bool store = mode == rse::kStore;
+  return Job{c->kfield, &rows, q.in.data(), store ? q.par.data() : nullptr,
+             store ? nullptr : q.par.data(), sb, mode, false, mismatch, (uint64_t)c->total * sb,
+             n_stripes, per_stripe};
+}
+
+// ---------------------------------------------------- rse_reconstruct_batch
+// Many stripes, each with its own erasure pattern, in two launches: the plan
+// (partition + k x k inverse + composed rows, core.rs:733-923) is computed per
+// stripe on the device, then every stripe is coded from its descriptor.  No
+// host round trip and no decode-matrix cache: a batch of distinct patterns
+// costs one inversion per stripe on the GPU instead of one per stripe on the
+// host.  Validation happens up front (on the host, or for large batches in a
+// device pass before anything is coded), so an error leaves every stripe
+// untouched.  The steps below, in the order rse_reconstruct_batch runs them.
+struct Batch {
+  const rse_codec* c;
+  uint8_t* base;
+  size_t shard_len, sb, n_stripes;
+  const uint8_t* present;  // the caller's flags
+  bool dev_flags;          // ... which are device memory
+  bool data_only;
+  hipStream_t st;
+  const uint8_t* dfl = nullptr;  // the flags the device reads: `present`, or the workspace's copy
+  uint32_t need = 0, e_cap = 0, nout_cap = 0;  // validation: the largest counts of any stripe
+};
+
+// What a call holds on the device from its first queued operation on: the
+// lease, its workspace (lease_plan: n_stripes * T flags, the scan's 6 result
+// words, then on the bit-sliced path the per-stripe descriptors; past
+// kPlanKeep the call's own allocation), the table step's descriptors and the
+// host rows that queued copies read.  The lease must go back to the pool idle,
+// and nothing queued may outlive the host memory it reads (these rows, the
+// caller's flags).  So every return after take() goes through finish(): the
+// call's allocations are freed on the stream, the stream is synchronised, and
+// only then does the destructor let the lease and the rows go.
+struct BatchWork {
+  hipStream_t st;
+  Lease lease;
+  uint8_t *ws = nullptr, *desc = nullptr;  // the workspace; the table step's descriptors
+  bool ws_owned = false;                   // past kPlanKeep: allocated for this call
+  Rows prow;                               // the bit-sliced step's host rows
+  explicit BatchWork(hipStream_t s) : st(s) {}
+  hipError_t take(size_t bytes) {
+    const hipError_t e = lease.acquire();
+    return e != hipSuccess ? e : lease_plan(lease.get(), bytes, st, &ws, &ws_owned);
+  }
+  hipError_t free_owned() {  // after the stream's work on them
+    const hipError_t e = desc ? hipFreeAsync(desc, st) : hipSuccess;
+    const hipError_t f = ws && ws_owned ? hipFreeAsync(ws, st) : hipSuccess;
+    desc = ws = nullptr;
+    return e != hipSuccess ? e : f;
+  }
+  int finish(int rc) {  // rc: the steps' status; the first error wins
+    const hipError_t f = free_owned();
+    const hipError_t y = hipStreamSynchronize(st);
+    if (rc != RSE_OK) return rc;
+    return f != hipSuccess ? dev_fail(f) : y != hipSuccess ? dev_fail(y) : RSE_OK;
+  }
+};
+
+int hip_rc(hipError_t e) { return e == hipSuccess ? RSE_OK : dev_fail(e); }
+
+// One stripe's validation (core.rs:747-772), and the batch's counts, which
+// the planners size their work by, raised to the stripe's: the highest sigma
+// row + 1 it uses (its syndrome rows R and missing parity rows), its missing
+// data shards and its outputs.
+int batch_stripe(Batch& b, const uint8_t* pr) {
+  const size_t k = b.c->k, p = b.c->p;
+  uint32_t ne = 0, nr = 0, nmp = 0, nd = 0;
+  for (size_t j = 0; j < k; ++j) ne += pr[j] ? 0u : 1u;
+  size_t np = k - ne;
+  for (size_t r = 0; r < p; ++r) {
+    const bool here = pr[k + r] != 0;
+    np += here ? 1 : 0;
+    const bool syn = here && nr < ne;
+    nr += syn ? 1u : 0u;
+    if (!here && !b.data_only) ++nmp;
+    if (syn || (!here && !b.data_only)) nd = (uint32_t)r + 1;
+  }
+  if (np && b.shard_len == 0) return RSE_EMPTY_SHARD;
+  if (np < k) return RSE_TOO_FEW_SHARDS_PRESENT;
+  b.need = std::max(b.need, nd);
+  b.e_cap = std::max(b.e_cap, ne);
+  b.nout_cap = std::max(b.nout_cap, ne + nmp);
+  return RSE_OK;
+}
+
+// Host validation of the n stripes whose flags are at `flags`: the first error.
+int batch_validate_host(Batch& b, const uint8_t* flags, size_t n) {
+  for (size_t s = 0; s < n; ++s)
+    if (const int rc = batch_stripe(b, flags + s * b.c->total)) return rc;
+  return RSE_OK;
+}
+
+// The first n stripes' flags on the host: the caller's, or a copy of its
+// device flags in `copy` (nullptr: the copy failed).
+const uint8_t* batch_host_flags(const Batch& b, size_t n, std::vector<uint8_t>& copy) {
+  if (!b.dev_flags) return b.present;
+  copy.resize(n * b.c->total);
+  const hipError_t e = hipMemcpy(copy.data(), b.present, copy.size(), hipMemcpyDeviceToHost);
+  return e == hipSuccess ? copy.data() : nullptr;
+}
+
+// Shared-pattern runs (host flags only).  Runs of consecutive stripes with one
+// erasure pattern (a lost disk: every stripe misses the same shards) go
+// through the shared-pattern path: one plan per run, and the pattern's own
+// kernel once it has one (core.rs:697-731 caches the pattern; used twice, it
+// is specialised), instead of a plan and a mixing per stripe.  Used when the
+// runs are long (at most one run per 16 stripes on average): *applies, and the
+// call's status.  Every run is validated before any runs.
+int batch_shared_runs(Batch& b, bool* applies) {
+  const size_t T = b.c->total, n_stripes = b.n_stripes;
+  std::vector<std::pair<size_t, size_t>> runs;  // [first, count)
+  for (size_t s0 = 0; s0 < n_stripes;) {
+    size_t s1 = s0 + 1;
+    while (s1 < n_stripes && std::memcmp(b.present + s1 * T, b.present + s0 * T, T) == 0) ++s1;
+    runs.emplace_back(s0, s1 - s0);
+    if (runs.size() * 16 > n_stripes) break;
+    // per-stripe patterns show in the first stripes: stop once a prefix
+    // holds many runs at over twice the admitted density (this only picks
+    // the faster path; both give the same bytes)
+    if (runs.size() >= 64 && runs.size() * 8 > s1) break;
+    s0 = s1;
+  }
+  size_t covered = 0;
+  for (auto& r : runs) covered += r.second;
+  *applies = covered == n_stripes && runs.size() * 16 <= n_stripes;
+  if (!*applies) return RSE_OK;
+  for (auto& r : runs)
+    if (const int rc = batch_stripe(b, b.present + r.first * T)) return rc;
+  if (b.nout_cap == 0) return RSE_OK;  // nothing this call rebuilds, in any run
+  for (auto& r : runs) {
+    const int rc = flat_reconstruct(b.c, b.base + r.first * T * b.sb, b.shard_len, r.second,
+                                    b.present + r.first * T, b.data_only, b.st);
+    if (rc) return rc;
+  }
+  return RSE_OK;
+}
+
+// Batches from this many stripes on are validated on the device (one
+// synchronisation instead of a host pass over every flag).
+constexpr size_t kDeviceScanStripes = 2048;
+
+// Validation on the device, one lane per stripe.  Host flags go up through the
+// lease's pinned words (an asynchronous DMA rather than the runtime's staged
+// pageable copy; only up to 16 MiB of flags: a lease keeps its words, and the
+// pool keeps up to kIdleScratch leases), the scan's results come back into
+// the first words: the one synchronisation before finish(), to read them.
+int batch_scan(Batch& b, BatchWork& w, size_t fl_bytes) {
+  const size_t nf = b.n_stripes * b.c->total;
+  const bool staged = !b.dev_flags && nf <= (size_t(16) << 20);
+  RSE_HIP(lease_words(w.lease.get(), 8 + (staged ? (nf + 3) / 4 : 0)));
+  uint32_t* wh = w.lease->wh;
+  uint32_t* res = reinterpret_cast<uint32_t*>(w.ws + fl_bytes);
+  if (!b.dev_flags) {
+    if (staged) std::memcpy(wh + 8, b.present, nf);
+    RSE_HIP(hipMemcpyAsync(w.ws, staged ? static_cast<const void*>(wh + 8) : b.present, nf,
+                           hipMemcpyHostToDevice, b.st));
+  }
+  RSE_HIP(hipMemsetAsync(res, 0, 4 * sizeof(uint32_t), b.st));
+  RSE_HIP(hipMemsetAsync(res + 4, 0xFF, 2 * sizeof(uint32_t), b.st));
+  RSE_HIP(rse::launch_batch_scan(b.dfl, b.n_stripes, (uint32_t)b.c->k, (uint32_t)b.c->p,
+                                 b.data_only ? 1u : 0u, res, b.st));
+  RSE_HIP(hipMemcpyAsync(wh, res, 6 * sizeof(uint32_t), hipMemcpyDeviceToHost, b.st));
+  RSE_HIP(hipStreamSynchronize(b.st));
+  const volatile uint32_t* v = wh;
+  b.need = v[0];
+  b.e_cap = v[1];
+  b.nout_cap = v[2];
+  // the first failing stripe: some stripe has too few shards
+  return ((uint64_t)v[5] << 32 | v[4]) != ~0ull ? RSE_TOO_FEW_SHARDS_PRESENT : RSE_OK;
+}
+
+// The bit-sliced step: whole 16 KiB chunks on the bit-sliced syndrome kernels
+// (compiled or run-time specialised codecs), planned per stripe on the device
+// into the descriptors at ws + desc_off.  *done: bytes of every shard coded.
+int batch_bitslice(const Batch& b, BatchWork& w, size_t desc_off, uint64_t* done) {
+  const rse_codec* c = b.c;
+  want_bitslice(c, b.sb, false, b.n_stripes);
+  if (b.need == 0) {  // nothing missing that this call rebuilds, in any stripe
+    *done = b.sb;
+    return RSE_OK;
+  }
+  // the parity rows and the planner's tables: the codec's device copy
+  const uint8_t* consts = nullptr;
+  RSE_HIP(plan_consts(c, &consts));
+  w.prow = parity_rows(c);  // read by queued copies: w's until finish()
+  RSE_HIP(rse::launch_bitslice_recon_batch(
+      c->kfield, (uint32_t)c->k, (uint32_t)c->p, w.prow.c.data(),
+      reinterpret_cast<const uint16_t*>(consts), consts + plan_tab_off(c), b.dfl,
+      b.data_only ? 1u : 0u, b.base, b.sb, (uint32_t)b.n_stripes, b.need, b.e_cap,
+      reinterpret_cast<rse::BsReconArgs*>(w.ws + desc_off), b.st, done));
+  return RSE_OK;
+}
+
+// The table step: bytes [done, sb) of every shard (all of it if the
+// bit-sliced step did not apply), planned per stripe on the device
+// (recon_plan_kernel: e x e syndrome inverse, composed rows as descriptors),
+// coded by the table kernels, in groups of at most 256 MiB of descriptors.
+int batch_tables(const Batch& b, BatchWork& w, size_t done) {
+  const rse_codec* c = b.c;
+  const size_t k = c->k, T = c->total, n_ib = (k + 31) / 32, n_ob = (b.nout_cap + 15) / 16;
+  const size_t per_stripe = n_ib * n_ob * sizeof(CodeArgs);
+  const size_t grp =
+      std::max<size_t>(1, std::min<size_t>(b.n_stripes, (size_t(256) << 20) / per_stripe));
+  const uint8_t* consts = nullptr;  // the parity rows on the device
+  RSE_HIP(plan_consts(c, &consts));
+  RSE_HIP(hipMallocAsync(reinterpret_cast<void**>(&w.desc), grp * per_stripe, b.st));
+  for (size_t g0 = 0; g0 < b.n_stripes; g0 += grp) {
+    const size_t ng = std::min(grp, b.n_stripes - g0);
+    RSE_HIP(rse::launch_recon_plan(c->kfield, reinterpret_cast<const uint16_t*>(consts),
+                                   b.dfl + g0 * T, (uint32_t)k, (uint32_t)T, b.data_only ? 1u : 0u,
+                                   b.e_cap, b.nout_cap, b.base + g0 * T * b.sb, b.sb, done,
+                                   b.sb - done, (uint32_t)ng, reinterpret_cast<CodeArgs*>(w.desc),
+                                   b.st));
+  }
+  return RSE_OK;
+}
+
+// The host-planner fallback, past the device planner's LDS budget: bytes
+// [done, sb) stripe by stripe through reconstruct_impl.  Nothing from here on
+// uses the call's workspace, so it is handed back first.
+int batch_host_planner(const Batch& b, BatchWork& w, size_t done) {
+  const rse_codec* c = b.c;
+  const size_t T = c->total;
+  (void)w.free_owned();  // queued behind the stream's work on it
+  std::vector<uint8_t> copy;
+  const uint8_t* hfl = batch_host_flags(b, b.n_stripes, copy);
+  if (!hfl) return dev_fail(hipGetLastError());
+  std::vector<void*> ptrs(T);
+  std::vector<size_t> lens(T, (b.sb - done) / c->esize());
+  for (size_t s = 0; s < b.n_stripes; ++s) {
+    for (size_t i = 0; i < T; ++i) ptrs[i] = b.base + (s * T + i) * b.sb + done;
+    const int rc = reconstruct_impl(c, ptrs.data(), lens.data(), hfl + s * T, T, b.data_only, b.st);
+    if (rc) return rc;
+    ++g_host_planned;
+  }
+  return RSE_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2223,16 +2471,11 @@ int rse_encode_flat(const rse_codec* c, void* stripes, size_t shard_len, size_t 
   if (shard_len == 0) return RSE_EMPTY_SHARD;
   if (n_stripes == 0) return RSE_OK;
   const size_t sb = shard_len * c->esize();
-  uint8_t* base = static_cast<uint8_t*>(stripes);
-  std::vector<const uint8_t*> in(c->k);
-  std::vector<uint8_t*> out(c->p);
-  for (size_t i = 0; i < c->k; ++i) in[i] = base + i * sb;
-  for (size_t r = 0; r < c->p; ++r) out[r] = base + (c->k + r) * sb;
   want_bitslice(c, sb, false, n_stripes);
   const Rows rows = parity_rows(c);
-  Job j{c->kfield, &rows, in.data(), out.data(), nullptr, sb, rse::kStore, false, nullptr,
-        (uint64_t)c->total * sb, n_stripes};
-  return run_job(j, (hipStream_t)stream);
+  FlatPtrs q;
+  return run_job(flat_job(c, rows, stripes, sb, n_stripes, rse::kStore, nullptr, false, q),
+                 (hipStream_t)stream);
 }
 
 int rse_verify_flat(const rse_codec* c, const void* stripes, size_t shard_len, size_t n_stripes,
@@ -2242,14 +2485,10 @@ int rse_verify_flat(const rse_codec* c, const void* stripes, size_t shard_len, s
   if (shard_len == 0) return RSE_EMPTY_SHARD;
   if (n_stripes == 0) return RSE_OK;
   const size_t sb = shard_len * c->esize();
-  const uint8_t* base = static_cast<const uint8_t*>(stripes);
-  std::vector<const uint8_t*> in(c->k), cmp(c->p);
-  for (size_t i = 0; i < c->k; ++i) in[i] = base + i * sb;
-  for (size_t r = 0; r < c->p; ++r) cmp[r] = base + (c->k + r) * sb;
   want_bitslice(c, sb, false, n_stripes);
   const Rows rows = parity_rows(c);
-  Job j{c->kfield, &rows, in.data(), nullptr, cmp.data(), sb, rse::kCheck, false, nullptr,
-        (uint64_t)c->total * sb, n_stripes, true};
+  FlatPtrs q;
+  const Job j = flat_job(c, rows, stripes, sb, n_stripes, rse::kCheck, nullptr, true, q);
   std::vector<int> res;
   try {
     res.resize(n_stripes);
@@ -2327,12 +2566,8 @@ int rse_scrub_flat(const rse_codec* c, void* stripes, size_t shard_len, size_t n
           uint32_t* list = listed && bad_stripes ? bad_stripes : words + n_stripes;
           uint32_t* count = listed && n_bad ? n_bad : words + 2 * n_stripes;
           RSE_HIP(hipMemsetAsync(words, 0, n_stripes * sizeof(uint32_t), st));
-          const uint8_t* base = static_cast<const uint8_t*>(stripes);
-          std::vector<const uint8_t*> in(c->k), cmp(c->p);
-          for (size_t i = 0; i < c->k; ++i) in[i] = base + i * sb;
-          for (size_t r = 0; r < c->p; ++r) cmp[r] = base + (c->k + r) * sb;
-          Job j{c->kfield, &rows, in.data(), nullptr, cmp.data(), sb, rse::kCheck, false, words,
-                (uint64_t)n * sb, n_stripes, true};
+          FlatPtrs q;
+          const Job j = flat_job(c, rows, stripes, sb, n_stripes, rse::kCheck, words, true, q);
           if (const int jr = run_job(j, st)) return jr;
           RSE_HIP(rse::launch_scrub_compact(words, present, n, nullptr, n_stripes, list, count, st));
           RSE_HIP(rse::launch_correct_list(ca, list, count, status, changed, counts, st));
@@ -2357,42 +2592,6 @@ int rse_reconstruct_data_flat(const rse_codec* c, void* stripes, size_t shard_le
                           (hipStream_t)stream);
 }
 
-// Many stripes, each with its own erasure pattern, in two launches: the plan
-// (partition + k x k inverse + composed rows, core.rs:733-923) is computed per
-// stripe on the device, then every stripe is coded from its descriptor.  No
-// host round trip and no decode-matrix cache: a batch of distinct patterns
-// costs one inversion per stripe on the GPU instead of one per stripe on the
-// host.  Validation happens up front (on the host, or for large batches in a
-// device pass before anything is coded), so an error leaves every stripe
-// untouched.
-// One stripe's validation (core.rs:747-772) and the counts the planners size
-// their work by: the highest sigma row + 1 it uses (its syndrome rows R and
-// missing parity rows), its missing data shards and its outputs.
-int batch_stripe(const uint8_t* pr, size_t k, size_t p, bool data_only, size_t shard_len,
-                 uint32_t* need, uint32_t* ne_out, uint32_t* nout) {
-  uint32_t ne = 0, nr = 0, nmp = 0, nd = 0;
-  for (size_t j = 0; j < k; ++j) ne += pr[j] ? 0u : 1u;
-  size_t np = k - ne;
-  for (size_t r = 0; r < p; ++r) {
-    const bool here = pr[k + r] != 0;
-    np += here ? 1 : 0;
-    const bool syn = here && nr < ne;
-    nr += syn ? 1u : 0u;
-    if (!here && !data_only) ++nmp;
-    if (syn || (!here && !data_only)) nd = (uint32_t)r + 1;
-  }
-  if (np && shard_len == 0) return RSE_EMPTY_SHARD;
-  if (np < k) return RSE_TOO_FEW_SHARDS_PRESENT;
-  *need = nd;
-  *ne_out = ne;
-  *nout = ne + nmp;
-  return RSE_OK;
-}
-
-// Batches from this many stripes on are validated on the device (one
-// synchronisation instead of a host pass over every flag).
-constexpr size_t kDeviceScanStripes = 2048;
-
 int rse_reconstruct_batch(const rse_codec* c, void* stripes, size_t shard_len, size_t n_stripes,
                           const uint8_t* present, int data_only, rse_stream_t stream) {
   RSE_ON_STREAM(stream);
@@ -2400,255 +2599,54 @@ int rse_reconstruct_batch(const rse_codec* c, void* stripes, size_t shard_len, s
   if (n_stripes == 0) return RSE_OK;
   const size_t k = c->k, p = c->p, T = c->total, sb = shard_len * c->esize();
   uint8_t* base = static_cast<uint8_t*>(stripes);
-  hipStream_t st = (hipStream_t)stream;
   // The flags may live in device memory (a scrubber that found the damage on
   // the GPU): then they are never copied; the scan and the planners read them
-  // where they are, and the shared-pattern detection below (a host pass) is
-  // skipped.  Paths that need them on the host copy them there.
-  int fdev = -1;
+  // where they are, and the shared-pattern detection (a host pass) is skipped.
+  // The paths that need them on the host copy them there (batch_host_flags).
+  int fdev = -1, sdev = -1;
   const bool dev_flags = device_memory(present, &fdev);
-  if (dev_flags) {
-    // device flags must sit on the stripes' device: the scan and the
-    // planners read them in place (peer memory would fault or crawl)
-    int sdev = -1;
-    if (!device_memory(base, &sdev) || sdev != fdev) return RSE_ERR_INVALID_ARGUMENT;
-  }
-  std::vector<uint8_t> hflags;  // host copy of device flags, made on demand
-  auto host_flags = [&](size_t n) -> const uint8_t* {
-    if (!dev_flags) return present;
-    if (hflags.size() < n * T) {
-      hflags.resize(n * T);
-      if (hipMemcpy(hflags.data(), present, n * T, hipMemcpyDeviceToHost) != hipSuccess)
-        return nullptr;
-    }
-    return hflags.data();
-  };
-  // Runs of consecutive stripes with one erasure pattern (a lost disk: every
-  // stripe misses the same shards) go through the shared-pattern path: one
-  // plan per run, and the pattern's own kernel once it has one (core.rs:
-  // 697-731 caches the pattern; used twice, it is specialised), instead of a
-  // plan and a mixing per stripe.  Used when the runs are long (at most one
-  // run per 16 stripes on average).  Every run is validated before any runs.
+  // device flags must sit on the stripes' device: the scan and the planners
+  // read them in place (peer memory would fault or crawl)
+  if (dev_flags && (!device_memory(base, &sdev) || sdev != fdev)) return RSE_ERR_INVALID_ARGUMENT;
+  Batch b{c, base, shard_len, sb, n_stripes, present, dev_flags, data_only != 0, (hipStream_t)stream};
   if (!dev_flags) {
-    std::vector<std::pair<size_t, size_t>> runs;  // [first, count)
-    for (size_t s0 = 0; s0 < n_stripes;) {
-      size_t s1 = s0 + 1;
-      while (s1 < n_stripes && std::memcmp(present + s1 * T, present + s0 * T, T) == 0) ++s1;
-      runs.emplace_back(s0, s1 - s0);
-      if (runs.size() * 16 > n_stripes) break;
-      // per-stripe patterns show in the first stripes: stop once a prefix
-      // holds many runs at over twice the admitted density (this only picks
-      // the faster path; both give the same bytes)
-      if (runs.size() >= 64 && runs.size() * 8 > s1) break;
-      s0 = s1;
-    }
-    size_t covered = 0;
-    for (auto& r : runs) covered += r.second;
-    if (covered == n_stripes && runs.size() * 16 <= n_stripes) {
-      uint32_t nout_any = 0;
-      for (auto& r : runs) {
-        uint32_t nd, ne, no;
-        const int rc = batch_stripe(present + r.first * T, k, p, data_only != 0, shard_len, &nd,
-                                    &ne, &no);
-        if (rc) return rc;
-        nout_any |= no;
-      }
-      if (nout_any == 0) return RSE_OK;
-      for (auto& r : runs) {
-        const int rc = flat_reconstruct(c, base + r.first * T * sb, shard_len, r.second,
-                                        present + r.first * T, data_only != 0, st);
-        if (rc) return rc;
-      }
-      return RSE_OK;
-    }
+    bool applies = false;
+    const int rc = batch_shared_runs(b, &applies);
+    if (applies) return rc;
   }
-  // Validation of every stripe, and the largest counts any stripe needs.
-  // The flags go to the device once (the planners read them there); a large
-  // batch is validated there too, one lane per stripe.
-  uint32_t need = 0, e_cap = 0, nout_cap = 0;
-  // The device workspace, the lease's (kept between calls): n_stripes * T
-  // flags, the scan's 6 result words, then (bit-sliced path) the per-stripe
-  // descriptors.  Every return after work was queued has synchronised the
-  // stream, so the lease goes back to the pool idle.
-  uint8_t* dflags = nullptr;
-  bool ws_owned = false;  // past kPlanKeep: allocated for this call
+  if (shard_len == 0) {  // stripe 0 fails: EmptyShard, or TooFewShardsPresent (none present)
+    std::vector<uint8_t> copy;
+    const uint8_t* f0 = batch_host_flags(b, 1, copy);
+    return f0 ? batch_validate_host(b, f0, 1) : dev_fail(hipGetLastError());
+  }
+  // Validation of every stripe before any is written, on the host or (large
+  // batches, device flags) in the device scan below.
+  const bool dev_scan = dev_flags || n_stripes >= kDeviceScanStripes;
+  if (!dev_scan) {
+    if (const int rc = batch_validate_host(b, present, n_stripes)) return rc;
+    if (b.nout_cap == 0) return RSE_OK;  // nothing this call rebuilds, in any stripe
+  }
   const size_t fl_bytes = (n_stripes * T + 255) & ~size_t(255);
   const size_t desc_off = (fl_bytes + 64 + 255) & ~size_t(255);
   const bool fits = k <= (size_t)kMaxIn && p <= (size_t)kMaxOut && n_stripes <= 0xffffffffu;
   const bool bs_path = fits && sb >= 4096 && sb % 16u == 0 && aligned16(base) &&
                        rse::get_option(RSE_OPT_BITSLICE);
-  auto release = [&](hipError_t e) {  // after the stream's work on the workspace
-    if (dflags && ws_owned) (void)hipFreeAsync(dflags, st);
-    dflags = nullptr;
-    return e;
-  };
-  if (shard_len == 0) {  // stripe 0 fails: EmptyShard, or TooFewShardsPresent (none present)
-    uint32_t nd, ne, no;
-    const uint8_t* f0 = host_flags(1);
-    if (!f0) return dev_fail(hipGetLastError());
-    return batch_stripe(f0, k, p, data_only != 0, shard_len, &nd, &ne, &no);
+  BatchWork w(b.st);  // from here on every return goes through w.finish()
+  int rc = hip_rc(w.take(desc_off + (bs_path ? n_stripes * sizeof(rse::BsReconArgs) : 0)));
+  b.dfl = dev_flags ? present : w.ws;
+  // the flags go to the device once (the planners read them there)
+  if (rc == RSE_OK)
+    rc = dev_scan ? batch_scan(b, w, fl_bytes)
+                  : hip_rc(hipMemcpyAsync(w.ws, present, n_stripes * T, hipMemcpyHostToDevice, b.st));
+  const bool work = rc == RSE_OK && b.nout_cap != 0;  // else nothing this call rebuilds
+  uint64_t done = 0;                                  // bytes of every shard coded so far
+  if (work && bs_path) rc = batch_bitslice(b, w, desc_off, &done);
+  if (work && rc == RSE_OK && done < sb) {
+    const bool past_lds = T > 0xffffu || rse::recon_plan_lds((uint32_t)k, (uint32_t)T, b.e_cap,
+                                                             b.nout_cap) > rse::kReconPlanLdsMax;
+    rc = past_lds ? batch_host_planner(b, w, done) : batch_tables(b, w, done);
   }
-  const bool dev_scan = dev_flags || n_stripes >= kDeviceScanStripes;
-  if (!dev_scan) {
-    for (size_t s = 0; s < n_stripes; ++s) {
-      uint32_t nd, ne, no;
-      const int rc = batch_stripe(present + s * T, k, p, data_only != 0, shard_len, &nd, &ne, &no);
-      if (rc) return rc;
-      need = std::max(need, nd);
-      e_cap = std::max(e_cap, ne);
-      nout_cap = std::max(nout_cap, no);
-    }
-    if (nout_cap == 0) return RSE_OK;  // nothing this call rebuilds, in any stripe
-  }
-  Lease lease;
-  RSE_HIP(lease.acquire());
-  RSE_HIP(lease_plan(lease.get(),
-                     desc_off + (bs_path ? n_stripes * sizeof(rse::BsReconArgs) : 0), st,
-                     &dflags, &ws_owned));
-  const uint8_t* dfl = dev_flags ? present : dflags;  // the flags the device reads
-  if (!dev_scan) {
-    hipError_t e = hipMemcpyAsync(dflags, present, n_stripes * T, hipMemcpyHostToDevice, st);
-    if (e != hipSuccess) return dev_fail(release(e));
-  } else {
-    // the flags through the lease's pinned words (an asynchronous DMA rather
-    // than the runtime's staged pageable copy), the scan's results back into
-    // the first words
-    // (pinned words only up to 16 MiB of flags: a lease keeps its words, and
-    // the pool keeps up to kIdleScratch leases)
-    const bool staged = !dev_flags && n_stripes * T <= (size_t(16) << 20);
-    hipError_t e = lease_words(lease.get(), 8 + (staged ? (n_stripes * T + 3) / 4 : 0));
-    uint32_t* res = reinterpret_cast<uint32_t*>(dflags + fl_bytes);
-    if (e == hipSuccess && !dev_flags) {
-      if (staged) std::memcpy(lease->wh + 8, present, n_stripes * T);
-      e = hipMemcpyAsync(dflags, staged ? static_cast<const void*>(lease->wh + 8) : present,
-                         n_stripes * T, hipMemcpyHostToDevice, st);
-    }
-    if (e == hipSuccess) e = hipMemsetAsync(res, 0, 4 * sizeof(uint32_t), st);
-    if (e == hipSuccess) e = hipMemsetAsync(res + 4, 0xFF, 2 * sizeof(uint32_t), st);
-    if (e == hipSuccess)
-      e = rse::launch_batch_scan(dfl, n_stripes, (uint32_t)k, (uint32_t)p, data_only ? 1u : 0u,
-                                 res, st);
-    if (e == hipSuccess)
-      e = hipMemcpyAsync(lease->wh, res, 6 * sizeof(uint32_t), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) {
-      (void)hipStreamSynchronize(st);
-      return dev_fail(release(e));
-    }
-    const volatile uint32_t* w = lease->wh;
-    need = w[0];
-    e_cap = w[1];
-    nout_cap = w[2];
-    if (((uint64_t)w[5] << 32 | w[4]) != ~0ull) {  // too few shards in some stripe
-      (void)release(hipSuccess);
-      return RSE_TOO_FEW_SHARDS_PRESENT;
-    }
-  }
-  if (nout_cap == 0) {  // nothing this call rebuilds, in any stripe
-    (void)release(hipSuccess);
-    RSE_HIP(hipStreamSynchronize(st));
-    return RSE_OK;
-  }
-  size_t done = 0;  // bytes of every shard coded so far
-  // host inputs of the copies below: alive until the stream is synchronised
-  const Rows prow = parity_rows(c);
-  // 1. whole 16 KiB chunks on the bit-sliced syndrome kernels (compiled or
-  //    run-time specialised codecs), planned per stripe on the device
-  if (bs_path) {
-    want_bitslice(c, sb, false, n_stripes);
-    if (need > 0) {
-      const Rows& rows = prow;
-      // the parity rows and the planner's tables: the codec's device copy
-      const uint8_t* consts = nullptr;
-      int dev = 0;
-      hipError_t e = hipGetDevice(&dev);
-      if (e == hipSuccess) e = plan_consts(c, dev, &consts);
-      if (e != hipSuccess) {
-        (void)hipStreamSynchronize(st);  // the flags' copy into the lease may be in flight
-        return dev_fail(release(e));
-      }
-      uint8_t* ws = dflags + desc_off;  // the descriptors
-      uint64_t bs_done = 0;
-      e = rse::launch_bitslice_recon_batch(
-          c->kfield, (uint32_t)k, (uint32_t)p, rows.c.data(),
-          reinterpret_cast<const uint16_t*>(consts), consts + plan_tab_off(c), dfl,
-          data_only ? 1u : 0u, base, sb, (uint32_t)n_stripes, need, e_cap,
-          reinterpret_cast<rse::BsReconArgs*>(ws), st, &bs_done);
-      if (e == hipSuccess && bs_done == sb) {
-        e = release(hipSuccess);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);  // `prow` dies next
-      }
-      if (e != hipSuccess) {
-        (void)hipStreamSynchronize(st);
-        return dev_fail(release(e));
-      }
-      done = bs_done;
-    } else {
-      (void)release(hipSuccess);
-      RSE_HIP(hipStreamSynchronize(st));
-      return RSE_OK;  // nothing missing that this call rebuilds, in any stripe
-    }
-  }
-  if (done == sb) return RSE_OK;
-  // 2. the rest of every shard (all of it if step 1 did not apply): planned
-  //    per stripe on the device (recon_plan_kernel: e x e syndrome inverse,
-  //    composed rows as descriptors), coded by the table kernels
-  if (T > 0xffffu ||
-      rse::recon_plan_lds((uint32_t)k, (uint32_t)T, e_cap, nout_cap) > rse::kReconPlanLdsMax) {
-    // past the device planner's LDS budget: the host planner, stripe by stripe
-    (void)release(hipSuccess);
-    const uint8_t* hfl = host_flags(n_stripes);
-    if (!hfl) {
-      (void)hipStreamSynchronize(st);
-      return dev_fail(hipGetLastError());
-    }
-    std::vector<void*> ptrs(T);
-    std::vector<size_t> lens(T, (sb - done) / c->esize());
-    for (size_t s = 0; s < n_stripes; ++s) {
-      for (size_t i = 0; i < T; ++i) ptrs[i] = base + (s * T + i) * sb + done;
-      int rc = reconstruct_impl(c, ptrs.data(), lens.data(), hfl + s * T, T, data_only != 0, st);
-      if (rc) {
-        (void)hipStreamSynchronize(st);  // step 1's copies read `prow`
-        return rc;
-      }
-      ++g_host_planned;
-    }
-    RSE_HIP(hipStreamSynchronize(st));
-    return RSE_OK;
-  }
-  const size_t n_ib = (k + 31) / 32, n_ob = (nout_cap + 15) / 16;
-  const size_t per_stripe = n_ib * n_ob * sizeof(CodeArgs);
-  // stripes per planning group: descriptors of at most 256 MiB at a time
-  const size_t grp = std::max<size_t>(1, std::min<size_t>(n_stripes, (size_t(256) << 20) / per_stripe));
-  const uint8_t* consts = nullptr;  // the parity rows on the device (plan_consts)
-  uint8_t* ws = nullptr;            // the descriptors
-  {
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e == hipSuccess) e = plan_consts(c, dev, &consts);
-    if (e == hipSuccess) e = hipMallocAsync(reinterpret_cast<void**>(&ws), grp * per_stripe, st);
-    if (e != hipSuccess) {
-      (void)hipStreamSynchronize(st);  // step 1's work and the flags' copy may be in flight
-      return dev_fail(release(e));
-    }
-  }
-  hipError_t e = hipSuccess;
-  for (size_t g0 = 0; g0 < n_stripes && e == hipSuccess; g0 += grp) {
-    const size_t ng = std::min(grp, n_stripes - g0);
-    e = rse::launch_recon_plan(c->kfield, reinterpret_cast<const uint16_t*>(consts), dfl + g0 * T,
-                               (uint32_t)k, (uint32_t)T, data_only ? 1u : 0u, e_cap, nout_cap,
-                               base + g0 * T * sb, sb, done, sb - done, (uint32_t)ng,
-                               reinterpret_cast<CodeArgs*>(ws), st);
-  }
-  const hipError_t f = hipFreeAsync(ws, st);
-  const hipError_t g = release(hipSuccess);
-  // `prow` and the caller's flags must outlive the copies that read them
-  const hipError_t y = hipStreamSynchronize(st);
-  if (e != hipSuccess) return dev_fail(e);
-  if (f != hipSuccess) return dev_fail(f);
-  if (g != hipSuccess) return dev_fail(g);
-  RSE_HIP(y);
-  return RSE_OK;
+  return w.finish(rc);
 }
 
 int rse_code_shards(int field, const uint8_t* rows, size_t n_out, size_t n_in,

@@ -685,6 +685,133 @@ def test_reconstruct_batch_many_stripes_and_errors(R):
     assert torch.equal(buf, snap)
 
 
+# The exits of rse_reconstruct_batch that the tests above do not reach: each
+# leaves through the call's one cleanup path.
+def batch_stripes(rng, field, k, p, nbytes, stripes):
+    """`stripes` stripes encoded by the oracle: uint8 [stripes, k + p, nbytes]."""
+    oc = O.Codec(field, k, p)
+    full = []
+    for _ in range(stripes):
+        st = rand_shards(rng, k, nbytes) + [np.zeros(nbytes, np.uint8) for _ in range(p)]
+        oc.encode(st)
+        full.append(np.stack(st))
+    return np.stack(full)
+
+
+def batch_run(r, want, present, dflags, data_only=False, n=None):
+    """want with its lost shards poisoned, through reconstruct_batch: the
+    buffer before the call and after it."""
+    v = want.copy()
+    v[~present] = 0x5A
+    d = dev(v.reshape(-1))
+    flags = torch.from_numpy(present).cuda() if dflags else present
+    r.reconstruct_batch(d, n or want.shape[2], want.shape[0], flags, data_only=data_only)
+    return v, host(d).reshape(want.shape)
+
+
+def test_reconstruct_batch_device_flags_too_few_shards(R):
+    """Device flags (validated by the device scan, with the lease taken), one
+    stripe with too few shards: the error, nothing written, no Scratch made or
+    lost, and the lease back idle: the next call on this thread uses it."""
+    k, p, n, stripes = 3, 2, 7, 5
+    rng = np.random.default_rng(501)
+    lib = R._lib.load()
+    r = R.galois_8.ReedSolomon(k, p)
+    want = batch_stripes(rng, 8, k, p, n, stripes)
+    present = np.ones((stripes, k + p), bool)
+    for s in range(stripes):
+        present[s, rng.choice(k + p, 1 + s % 2, replace=False)] = False
+    assert (batch_run(r, want, present, True)[1] == want).all()  # leaves a lease idle in the pool
+    live = lib.rse_get_option(24)  # RSE_OPT_SCRATCH_LIVE
+    bad = present.copy()
+    bad[2] = [False, False, False, True, True]
+    v = want.copy()
+    v[~bad] = 0x5A
+    d = dev(v.reshape(-1))
+    snap = d.clone()
+    with pytest.raises(R.RSError) as ei:
+        r.reconstruct_batch(d, n, stripes, torch.from_numpy(bad).cuda())
+    assert ei.value.error == R.Error.TooFewShardsPresent
+    torch.cuda.synchronize()
+    assert torch.equal(d, snap)
+    assert lib.rse_get_option(24) == live
+    assert (batch_run(r, want, present, True)[1] == want).all()
+    assert lib.rse_get_option(24) == live
+
+
+def test_reconstruct_batch_device_flags_all_present(R):
+    """Device flags, every shard present: the scan finds nothing to rebuild,
+    so nothing is written and no kernel but the scan runs."""
+    k, p, n, stripes = 3, 2, 7, 5
+    lib = R._lib.load()
+    r = R.galois_8.ReedSolomon(k, p)
+    # not codewords: a rebuilt shard would differ from what is there
+    want = np.random.default_rng(502).integers(0, 256, (stripes, k + p, n), dtype=np.uint8)
+    n0 = lib.rse_get_option(6)
+    v, got = batch_run(r, want, np.ones((stripes, k + p), bool), True)
+    assert (got == v).all()
+    assert lib.rse_get_option(6) == n0
+
+
+@pytest.mark.parametrize("dflags", [False, True])
+def test_reconstruct_batch_table_path_parity_only(R, dflags):
+    """Only parity lost, shards too short for the bit-sliced path: with
+    data_only nothing is written (host flags: before any device work; device
+    flags: after the scan); without it the table path rebuilds the parity."""
+    k, p, n, stripes = 3, 2, 7, 5
+    rng = np.random.default_rng(503)
+    lib = R._lib.load()
+    r = R.galois_8.ReedSolomon(k, p)
+    want = batch_stripes(rng, 8, k, p, n, stripes)
+    present = np.ones((stripes, k + p), bool)
+    for s in range(stripes):
+        present[s, k + rng.choice(p, 1 + s % 2, replace=False)] = False
+    n0 = lib.rse_get_option(6)
+    v, got = batch_run(r, want, present, dflags, data_only=True)
+    assert (got == v).all()
+    assert (batch_run(r, want, present, dflags)[1] == want).all()
+    assert lib.rse_get_option(6) == n0  # 7-byte shards: never the bit-sliced step
+
+
+@pytest.mark.parametrize("dflags", [False, True])
+def test_reconstruct_batch_bitslice_path_nothing_to_rebuild(R, dflags):
+    """Shards the bit-sliced step takes, some stripes with lost parity only,
+    data_only: nothing for the call to rebuild, so it writes nothing and
+    launches no bit-sliced kernel."""
+    k, p, n, stripes = 10, 4, 16384, 5
+    rng = np.random.default_rng(504)
+    lib = R._lib.load()
+    r = R.galois_8.ReedSolomon(k, p)
+    want = rng.integers(0, 256, (stripes, k + p, n), dtype=np.uint8)
+    present = np.ones((stripes, k + p), bool)
+    for s in (1, 2, 4):
+        present[s, k + rng.choice(p, s, replace=False)] = False
+    n0 = lib.rse_get_option(6)
+    v, got = batch_run(r, want, present, dflags, data_only=True)
+    assert (got == v).all()
+    assert lib.rse_get_option(6) == n0
+
+
+def test_reconstruct_batch_after_host_planner_fallback(R):
+    """A batch past the device planner's LDS budget (planned on the host,
+    stripe by stripe, after the workspace is handed back), then an ordinary
+    batch on the same thread: both right, and only the first counts
+    host-planned stripes."""
+    lib = R._lib.load()
+    rng = np.random.default_rng(505)
+    h0 = lib.rse_get_option(25)  # RSE_OPT_HOST_PLANNED_STRIPES
+    for field, k, p, n, stripes, planned in [(16, 1, 40000, 8, 2, 2), (8, 3, 2, 7, 5, 0)]:
+        es = field // 8
+        r = R.core.ReedSolomon(k, p, field)
+        want = batch_stripes(rng, field, k, p, n * es, stripes)
+        present = np.ones((stripes, k + p), bool)
+        for s in range(stripes):
+            present[s, rng.choice(k + p, 1 + s % 2, replace=False)] = False
+        assert (batch_run(r, want, present, False, n=n)[1] == want).all()
+        assert lib.rse_get_option(25) - h0 == planned
+        h0 += planned
+
+
 @pytest.mark.parametrize("field,k,p", [(16, 20, 8), (8, 10, 4), (8, 10, 2)])
 @pytest.mark.parametrize("chunks,extra", [(1, 0), (3, 16), (2, 2), (6, 1717),
                                           (0, 4096), (1, 12336), (2, 8194)])  # 4 KiB chunks
