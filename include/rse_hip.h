@@ -288,6 +288,53 @@ int rse_scrub_flat(const rse_codec *codec, void *stripes, size_t shard_len, size
                    uint32_t *bad_stripes,  /* nullable, n_stripes */
                    uint32_t *n_bad,        /* nullable, 1 */
                    rse_stream_t stream);
+/* rse_scrub_flat for shards that are allocated separately: one pointer per
+ * shard, as rse_verify takes them, and a verdict per BLOCK of columns.
+ *   shards, lens  HOST arrays of k + p entries; shards[i] is DEVICE memory, data
+ *                 shards first and parity after; lens in elements, all equal.
+ *                 The shards must not overlap (not checked).
+ *   block_len     in elements; 0 = one block, the whole shard.  With
+ *                 len = lens[0]: B = min(block_len, len) (len for 0) and
+ *                 n_blocks = ceil(len / B).  Block b is elements
+ *                 [b B, min((b+1) B, len)) of every shard: only the last block
+ *                 may be shorter.
+ * A block is to this entry what a stripe is to rse_scrub_flat, and every
+ * sentence of that entry's contract holds with "block" for "stripe": every byte
+ * column decoded on its own, erasures beside errors with 2 nu + f <= p per
+ * column, a block with f > p neither read nor written, saturating counts, the
+ * ascending list whose entries from n_bad on are not written, GF(2^16) codecs of
+ * at most 255 shards decoded byte by byte.  `present` (nullable), `status`,
+ * `changed`, `counts` (nullable), `bad_blocks` and `n_bad` (nullable, each
+ * alone) are DEVICE memory with one row per block.  Defining property: the
+ * bytes of block b and its rows of the outputs after the call equal those of
+ * rse_scrub_flat run on the flat arrangement of block b alone, with shard_len =
+ * that block's length and `present` row b.
+ * Codecs: rse_scrub_flat's.  Routes: rse_scrub_flat's two, chosen once per
+ * call by the same rule over the block's bytes and every pointer: the check
+ * pass first where it runs on bit-sliced or FFT kernels now, B x element size is
+ * 1 KiB, 2 KiB or at least 4 KiB and a multiple of 16, and every shards[i] is
+ * 16-byte aligned; RSE_OPT_SCRUB_ROUTE forces either.  A shorter last block
+ * follows the call's route.  The repair pass reads 16 bytes per lane only when
+ * every shards[i] and the block's bytes are multiples of 16, else byte by byte.
+ * rse_last_kernel(): "scrub-shards gf8 10+4 prefilter" / "... direct".
+ * Asynchronous on `stream`, no host synchronisation; the host arrays are
+ * consumed before the call returns; every workspace is a stream-ordered
+ * allocation of the call.
+ * Validation, before any device call, in this order: NULL codec / shards / lens
+ * / status -> RSE_ERR_INVALID_ARGUMENT; a codec out of scope ->
+ * RSE_ERR_INVALID_ARGUMENT; n_shards != k + p -> RSE_TOO_FEW_SHARDS /
+ * RSE_TOO_MANY_SHARDS; lens[0] == 0 -> RSE_EMPTY_SHARD, unequal lens ->
+ * RSE_INCORRECT_SHARD_SIZE; a NULL shards[i] -> RSE_ERR_INVALID_ARGUMENT;
+ * n_blocks > 2^32 - 1 -> RSE_ERR_INVALID_ARGUMENT. */
+int rse_scrub_shards(const rse_codec *codec, void *const *shards, const size_t *lens,
+                     size_t n_shards, size_t block_len,
+                     const uint8_t *present, /* nullable, DEVICE, n_blocks x (k+p) */
+                     uint8_t *status,        /* DEVICE, n_blocks: RSE_CORRECT_* */
+                     uint8_t *changed,       /* nullable, n_blocks x (k+p) */
+                     uint32_t *counts,       /* nullable, n_blocks x 2 */
+                     uint32_t *bad_blocks,   /* nullable, n_blocks */
+                     uint32_t *n_bad,        /* nullable, 1 */
+                     rse_stream_t stream);
 /* Same layout; every stripe has the same erasure pattern `present[k+p]`
  * (wasm reconstruct(): reconstruct_data semantics). */
 int rse_reconstruct_data_flat(const rse_codec *codec, void *stripes, size_t shard_len,

@@ -31,6 +31,7 @@
 #include "rse_fft.hpp"
 #include "rse_fft16.hpp"
 #include "rse_correct.hpp"
+#include "rse_scrub_shards_plan.hpp"
 #include "rse_correct_plan.hpp"
 #include "rse_locate.hpp"
 #include "rse_locate_plan.hpp"
@@ -268,7 +269,7 @@ hipError_t run_chunk(const Job& j, size_t o0, size_t no, size_t i0, size_t ni, u
 // Shard lengths the bit-sliced kernels code (some of): at least one 4 KiB
 // chunk, or exactly 1 or 2 KiB (4 / 2 stripes per chunk, RSE_OPT_SUB_CHUNKS).
 bool bitslice_len(size_t len) {
-  return len >= 4096 || ((len == 1024 || len == 2048) && rse::get_option(RSE_OPT_SUB_CHUNKS));
+  return rse::chunk_kernels_len(len, rse::get_option(RSE_OPT_SUB_CHUNKS) != 0);
 }
 
 // Is every pointer the job's mode touches 16-byte aligned?
@@ -2132,21 +2133,20 @@ int locate_pass(const rse_codec* c, const void* stripes, size_t shard_len, size_
   return rc;
 }
 
-// Which route rse_scrub_flat takes over `shard_bytes` of every shard (DESIGN
-// §4.L3): true, pre-filter -- the check pass of rse_verify_flat first, the
+// Which route rse_scrub_flat and rse_scrub_shards take: true,
+// pre-filter -- the check pass of rse_verify_flat first, the
 // repair over the stripes it failed -- when that check runs on bit-sliced or
 // FFT kernels now: kernels of the codec's own that exist (a module still
 // building is not waited for, and a wide codec never pays its table check),
-// and a shard length and alignment they take (run_job).  False, direct: the
-// repair pass over every stripe.  RSE_OPT_SCRUB_ROUTE 0 / 2 force either.
-// rows: the codec's parity rows.
-bool scrub_prefilters(const rse_codec* c, const Rows& rows, const void* stripes,
-                      size_t shard_bytes) {
+// and a shard length and alignment they take (run_job) -- `fits`: the bytes
+// of a stripe's shard satisfy bitslice_len and are a multiple of 16, and every
+// shard starts on a 16-byte boundary.  False, direct: the repair pass over
+// every stripe.  RSE_OPT_SCRUB_ROUTE 0 / 2 force either.  rows: the codec's
+// parity rows.
+bool scrub_prefilters(const rse_codec* c, const Rows& rows, bool fits) {
   const int64_t route = rse::get_option(RSE_OPT_SCRUB_ROUTE);
   if (route != 1) return route == 2;
-  if (!bitslice_len(shard_bytes) || shard_bytes % 16u != 0 || !aligned16(stripes) ||
-      !rse::get_option(RSE_OPT_BITSLICE))
-    return false;
+  if (!fits || !rse::get_option(RSE_OPT_BITSLICE)) return false;
   const int kind = kernel_kind_of(c, rows, 0);
   return kind == RSE_KERNELS_COMPILED || kind == RSE_KERNELS_SPECIALISED ||
          kind == RSE_KERNELS_FFT;
@@ -2553,7 +2553,8 @@ int rse_scrub_flat(const rse_codec* c, void* stripes, size_t shard_len, size_t n
   // pre-filter route too
   want_bitslice(c, sb, false, n_stripes);
   const Rows rows = parity_rows(c);
-  const bool pre = scrub_prefilters(c, rows, stripes, sb);
+  const bool pre =
+      scrub_prefilters(c, rows, bitslice_len(sb) && sb % 16u == 0 && aligned16(stripes));
   const uint32_t n = (uint32_t)c->total;
   const int rc = locate_run(
       c, stripes, sb, n_stripes, pre ? 2 * n_stripes + 1 : 0, stream,
@@ -2581,6 +2582,80 @@ int rse_scrub_flat(const rse_codec* c, void* stripes, size_t shard_len, size_t n
       });
   if (rc == RSE_OK)
     rse::note_kernel("scrub gf%d %zu+%zu %s", c->field, c->k, c->p, pre ? "prefilter" : "direct");
+  return rc;
+}
+
+// rse_scrub_flat for separately allocated shards, a block of block_len
+// elements of every shard in the place of a stripe (rse_scrub_shards_plan.hpp).
+// The same two routes.  The check pass takes pointers as they are: one job
+// over the full blocks, stripe stride = the block's bytes, and one over the
+// shorter last block, whose verdict is the last word.  The repair kernels
+// read the pointers from their arguments and know the last block's length, so
+// one sweep, one finalize and one compaction serve all the blocks.
+int rse_scrub_shards(const rse_codec* c, void* const* shards, const size_t* lens, size_t n_shards,
+                     size_t block_len, const uint8_t* present, uint8_t* status, uint8_t* changed,
+                     uint32_t* counts, uint32_t* bad_blocks, uint32_t* n_bad,
+                     rse_stream_t stream) {
+  if (!c || !shards || !lens || !status) return RSE_ERR_INVALID_ARGUMENT;
+  if (!rse::locate_in_scope(RSE_FIELD_GF8, c->k, c->p)) return RSE_ERR_INVALID_ARGUMENT;
+  int rc;
+  if ((rc = check_count(n_shards, c->total, RSE_TOO_FEW_SHARDS, RSE_TOO_MANY_SHARDS))) return rc;
+  if ((rc = check_multi(lens, n_shards))) return rc;
+  for (size_t i = 0; i < n_shards; ++i)
+    if (!shards[i]) return RSE_ERR_INVALID_ARGUMENT;
+  const rse::ScrubShardsPlan pl =
+      rse::scrub_shards_plan(lens[0], block_len, c->esize(), shards, n_shards,
+                             rse::get_option(RSE_OPT_SUB_CHUNKS) != 0);
+  if (pl.n_blocks > 0xffffffffu) return RSE_ERR_INVALID_ARGUMENT;
+  static_assert(sizeof(uint8_t*) == sizeof(void*), "pointer tables");
+  if (c->total > rse::kCorMaxShards) return RSE_ERR_INVALID_ARGUMENT;  // locate_in_scope: never
+  const size_t nb = pl.n_blocks;
+  want_bitslice(c, pl.block_bytes, false, nb);  // as rse_scrub_flat
+  const Rows rows = parity_rows(c);
+  const bool pre = scrub_prefilters(c, rows, pl.len_prefilters && pl.vec);
+  const uint32_t n = (uint32_t)c->total;
+  rc = locate_run(
+      c, nullptr, pl.block_bytes, nb, pre ? 2 * nb + 1 : 0, stream,
+      [&](const rse::LocateArgs& a, hipStream_t st) {
+        rse::CorrectShardsArgs sa{};
+        sa.cor = rse::CorrectArgs{a, present};
+        sa.tail_bytes = pl.tail_bytes;
+        sa.vec = pl.vec ? 1u : 0u;
+        for (size_t i = 0; i < n_shards; ++i) sa.ptr[i] = static_cast<const uint8_t*>(shards[i]);
+        const uint32_t *list = nullptr, *count = nullptr;
+        bool listed = false;  // the caller's list is written already
+        if (pre) {
+          uint32_t* words = a.acc + nb * rse::kLocAccWords;
+          listed = present == nullptr;
+          uint32_t* wl = listed && bad_blocks ? bad_blocks : words + nb;
+          uint32_t* wc = listed && n_bad ? n_bad : words + 2 * nb;
+          RSE_HIP(hipMemsetAsync(words, 0, nb * sizeof(uint32_t), st));
+          const Job full{c->kfield, &rows, sa.ptr, nullptr, sa.ptr + c->k, pl.block_bytes,
+                         rse::kCheck, false, words, pl.block_bytes, (size_t)pl.n_full, true};
+          if (const int jr = run_job(full, st)) return jr;
+          if (pl.tail_bytes != 0) {  // the last block: the same pointers, past the full blocks
+            std::vector<const uint8_t*> q(sa.ptr, sa.ptr + n);
+            for (auto& ptr : q) ptr += pl.n_full * pl.block_bytes;
+            Job tail = full;
+            tail.in = q.data();
+            tail.cmp = q.data() + c->k;
+            tail.len_bytes = pl.tail_bytes;
+            tail.mismatch = words + pl.n_full;
+            tail.n_stripes = 1;
+            if (const int jr = run_job(tail, st)) return jr;
+          }
+          RSE_HIP(rse::launch_scrub_compact(words, present, n, nullptr, nb, wl, wc, st));
+          list = wl;
+          count = wc;
+        }
+        RSE_HIP(rse::launch_correct_shards(sa, list, count, status, changed, counts, st));
+        if (!listed && (bad_blocks || n_bad))
+          RSE_HIP(rse::launch_scrub_compact(nullptr, nullptr, n, status, nb, bad_blocks, n_bad, st));
+        return (int)RSE_OK;
+      });
+  if (rc == RSE_OK)
+    rse::note_kernel("scrub-shards gf%d %zu+%zu %s", c->field, c->k, c->p,
+                     pre ? "prefilter" : "direct");
   return rc;
 }
 

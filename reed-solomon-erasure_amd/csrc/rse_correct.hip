@@ -23,6 +23,10 @@
 // rse_scrub_flat's pre-filter route runs the same stripe body over a device
 // list of stripes (correct_list_kernel); scrub_compact_kernel makes that list,
 // and the caller's list of stripes that did not end CLEAN.
+//
+// rse_scrub_shards runs both sweep kernels over separately allocated shards:
+// the kernels are instantiated a second time for CorrectShardsArgs, whose
+// layout (rse_locate_core.hpp LocPtrs) reads a shard's address from a table.
 #include "rse_correct.hpp"
 #include "rse_correct_plan.hpp"
 #include "rse_locate_core.hpp"
@@ -46,10 +50,10 @@ struct CorLds {
 // The rare path: the lane's bad byte columns through the column decoder, the
 // error values XORed into the stripe.  Rolled over the columns with the
 // accumulators picked apart by selects, as rse_locate.hip's loc_slow.
-template <int NO, int NW>
+// col0(r): the first of the lane's columns in shard r (a layout's cursor).
+template <int NO, int NW, class Cursor>
 __device__ __forceinline__ void cor_slow(const CorLds& l, const uint32_t (&acc)[NO][NW],
-                                         uint32_t p, uint32_t n, uint8_t* col0,
-                                         uint64_t shard_bytes) {
+                                         uint32_t p, uint32_t n, const Cursor& col0) {
   uint32_t stored = 0u, bad = 0u;  // of the lane's columns: one atomic each at the end
 #pragma unroll 1
   for (uint32_t c = 0; c < (NW == 1 ? 1u : 4u * NW); ++c) {
@@ -67,7 +71,7 @@ __device__ __forceinline__ void cor_slow(const CorLds& l, const uint32_t (&acc)[
       const uint32_t e = pk_get(val, i);
       if (e == 0u) continue;
       const uint32_t r = pk_get(pos, i);
-      gptr<uint8_t> q = (gptr<uint8_t>)(col0 + (uint64_t)r * shard_bytes + c);
+      gptr<uint8_t> q = (gptr<uint8_t>)(const_cast<uint8_t*>(col0(r)) + c);
       *q = (uint8_t)(*q ^ e);
       // a whole bad shard sets the same bit in every column: look before the atomic
       if (((l.mask[r >> 5] >> (r & 31u)) & 1u) == 0u) atomicOr(&l.mask[r >> 5], 1u << (r & 31u));
@@ -131,12 +135,34 @@ __device__ __forceinline__ void cor_enter(const CorShared& sh, const CorrectArgs
   __syncthreads();
 }
 
+// What a sweep kernel gets as its argument: CorrectArgs, the flat layout, or
+// CorrectShardsArgs.  cor_args: the part both have; cor_layout: where stripe
+// `stripe` lies.  The last block of separately allocated shards has its own
+// length, and vectors only as far as it has whole ones.
+__host__ __device__ __forceinline__ CorrectArgs& cor_args(CorrectArgs& ca) { return ca; }
+__host__ __device__ __forceinline__ CorrectArgs& cor_args(CorrectShardsArgs& sa) { return sa.cor; }
+__device__ __forceinline__ const CorrectArgs& cor_args(const CorrectArgs& ca) { return ca; }
+__device__ __forceinline__ const CorrectArgs& cor_args(const CorrectShardsArgs& sa) {
+  return sa.cor;
+}
+__device__ __forceinline__ LocFlat cor_layout(const CorrectArgs& ca, uint64_t stripe) {
+  const LocateArgs& a = ca.loc;
+  const uint64_t stride = (uint64_t)(a.k + a.p) * a.shard_bytes;
+  return LocFlat{a.base + stripe * stride, a.shard_bytes, a.n_vec};
+}
+__device__ __forceinline__ LocPtrs cor_layout(const CorrectShardsArgs& sa, uint64_t stripe) {
+  const LocateArgs& a = sa.cor.loc;
+  const bool tail = sa.tail_bytes != 0 && stripe == a.n_stripes - 1;
+  const uint64_t len = tail ? sa.tail_bytes : a.shard_bytes;
+  return LocPtrs{sa.ptr, stripe * a.shard_bytes, len, sa.vec != 0u ? len / 16u : 0u};
+}
+
 // One stripe by one workgroup, which takes `part` of its units: the stripe's
 // erasures, the sweep, the workgroup's account of it.  Called by every thread;
 // the LDS state is left as cor_enter made it.
-template <int NO, bool MULTI, class Part>
+template <int NO, bool MULTI, class Lay, class Part>
 __device__ __forceinline__ void cor_stripe(const CorShared& sh, const CorrectArgs& ca,
-                                           uint64_t stripe, const Part& part) {
+                                           const Lay& lay, uint64_t stripe, const Part& part) {
   const LocateArgs& a = ca.loc;
   const uint32_t p = a.p, n = a.k + a.p, tid = threadIdx.x;
   const uint8_t* tabs = reinterpret_cast<const uint8_t*>(sh.tab);
@@ -164,11 +190,10 @@ __device__ __forceinline__ void cor_stripe(const CorShared& sh, const CorrectArg
   }
   const CorLds l{tabs + kLocLogOff, tabs + kLocExpOff, tabs + kLocTOff, tabs + 1024,
                  CorrectErasures{f, sh.epos, sh.gamma, sh.emask}, sh.mask, sh.cnt};
-  const auto slow = [&](const auto& acc, const uint8_t* sbase, uint64_t off) {
-    cor_slow(l, acc, p, n, const_cast<uint8_t*>(sbase) + off, a.shard_bytes);
+  const auto slow = [&](const auto& acc, const Lay& at, uint64_t off) {
+    cor_slow(l, acc, p, n, at.from(0u, off));
   };
-  const uint64_t stride = (uint64_t)n * a.shard_bytes;
-  loc_sweep<NO, MULTI>(a, sh.tq, sh.tt2, a.base + stripe * stride, slow, part);
+  loc_sweep<NO, MULTI>(a, sh.tq, sh.tt2, lay, slow, part);
   // the workgroup's account of this stripe, one atomic per touched word
   __syncthreads();
   if (tid < 8) {
@@ -189,12 +214,13 @@ __device__ __forceinline__ void cor_stripe(const CorShared& sh, const CorrectArg
 }
 
 // Every stripe: grid.x workgroups share a stripe, grid.y stripes are in flight.
-template <int NO, bool MULTI>
-__global__ __launch_bounds__(kLocBlock) void correct_kernel(const CorrectArgs ca) {
+template <int NO, bool MULTI, class Args = CorrectArgs>
+__global__ __launch_bounds__(kLocBlock) void correct_kernel(const Args args) {
   COR_SHARED(NO, sh);
+  const CorrectArgs& ca = cor_args(args);
   cor_enter<NO, MULTI>(sh, ca);
   for (uint64_t stripe = blockIdx.y; stripe < ca.loc.n_stripes; stripe += gridDim.y)
-    cor_stripe<NO, MULTI>(sh, ca, stripe, LocGridPart{});
+    cor_stripe<NO, MULTI>(sh, ca, cor_layout(args, stripe), stripe, LocGridPart{});
 }
 
 // The stripes list[0 .. *n_list) only (rse_scrub_flat's work list: both are
@@ -203,19 +229,22 @@ __global__ __launch_bounds__(kLocBlock) void correct_kernel(const CorrectArgs ca
 // workgroups for (at most one per unit), and the (stripe, part) pairs are
 // walked with the grid's stride.  A workgroup without a pair returns before it
 // builds any table: an empty list costs the launch.
-template <int NO, bool MULTI>
+template <int NO, bool MULTI, class Args = CorrectArgs>
 __global__ __launch_bounds__(kLocBlock) void correct_list_kernel(
-    const CorrectArgs ca, const uint32_t* __restrict__ list, const uint32_t* __restrict__ n_list) {
+    const Args args, const uint32_t* __restrict__ list, const uint32_t* __restrict__ n_list) {
   COR_SHARED(NO, sh);
+  const CorrectArgs& ca = cor_args(args);
   const uint64_t cnt = *n_list, units = loc_units(ca.loc);
   uint64_t parts = cnt != 0 ? gridDim.x / cnt : 0;
   parts = parts < 1 ? 1 : parts > units ? units : parts;
   const uint64_t work = cnt * parts;
   if (blockIdx.x >= work) return;
   cor_enter<NO, MULTI>(sh, ca);
-  for (uint64_t w = blockIdx.x; w < work; w += gridDim.x)
-    cor_stripe<NO, MULTI>(sh, ca, list[w / parts],
+  for (uint64_t w = blockIdx.x; w < work; w += gridDim.x) {
+    const uint64_t stripe = list[w / parts];
+    cor_stripe<NO, MULTI>(sh, ca, cor_layout(args, stripe), stripe,
                           CorListPart{(uint32_t)(w % parts), (uint32_t)parts});
+  }
 }
 
 // One thread per (stripe, shard): changed flags; the thread of shard 0 also
@@ -308,43 +337,68 @@ hipError_t launch_scrub_compact(const uint32_t* words, const uint8_t* present, u
   return hipGetLastError();
 }
 
+namespace {
+
+// The two passes of every entry above.  `a` is the sweep kernels' argument of
+// either layout, `al` whether the layout admits 16-byte vectors; with a list
+// the first pass is over the stripes list[0 .. *n_list), else over all.
+template <class Args>
+hipError_t cor_launch(Args& a, bool al, const uint32_t* list, const uint32_t* n_list,
+                      uint8_t* status, uint8_t* changed, uint32_t* counts, hipStream_t stream) {
+  static_assert(kCorAccBad == kCorAccStored + 2 && kCorAccSkipped < kLocAccWords, "accumulator");
+  static_assert(sizeof(Args) + 2 * sizeof(void*) <= 4096, "the kernel-argument block");
+  int dev = 0, cus = 0;
+  if (list != nullptr) {
+    hipError_t e = hipGetDevice(&dev);
+    if (e == hipSuccess)
+      e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    if (e != hipSuccess) return e;
+  }
+  LocateArgs& loc = cor_args(a).loc;
+  return loc_launch(
+      loc, al, stream,
+      [&](auto no, auto multi, dim3 grid) {
+        constexpr int NO = decltype(no)::value;
+        constexpr bool MULTI = decltype(multi)::value;
+        if (list == nullptr) {
+          hipLaunchKernelGGL((correct_kernel<NO, MULTI, Args>), grid, dim3(kLocBlock), 0, stream,
+                             a);
+          return;
+        }
+        // loc_grid's shape is by the stripe count: not used.  Four workgroups per CU:
+        // sizing it by what the device holds at once (5 per CU at p <= 4, 3 above) was
+        // tried: no faster at 10+4, slower at 100+16
+        const dim3 lgrid((uint32_t)(cus > 0 ? cus : 1) * 4u);
+        hipLaunchKernelGGL((correct_list_kernel<NO, MULTI, Args>), lgrid, dim3(kLocBlock), 0,
+                           stream, a, list, n_list);
+      },
+      [&](dim3 blocks) {
+        hipLaunchKernelGGL(correct_finalize_kernel, blocks, dim3(256), 0, stream, loc.acc,
+                           loc.n_stripes, loc.k + loc.p, status, changed, counts);
+      });
+}
+
+}  // namespace
+
 hipError_t launch_correct_list(const CorrectArgs& args, const uint32_t* list,
                                const uint32_t* n_list, uint8_t* status, uint8_t* changed,
                                uint32_t* counts, hipStream_t stream) {
-  int dev = 0, cus = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  if (e != hipSuccess) return e;
+  if (list == nullptr) return hipErrorInvalidValue;
   CorrectArgs a = args;
-  return loc_launch(
-      a.loc, stream,
-      [&](auto no, auto multi, dim3) {  // loc_grid's shape is by the stripe count: not used
-        // four workgroups per CU.  Sizing it by what the device holds at once (5 per CU at
-        // p <= 4, 3 above) was tried: no faster at 10+4, slower at 100+16
-        const dim3 grid((uint32_t)(cus > 0 ? cus : 1) * 4u);
-        const auto kernel = correct_list_kernel<decltype(no)::value, decltype(multi)::value>;
-        hipLaunchKernelGGL(kernel, grid, dim3(kLocBlock), 0, stream, a, list, n_list);
-      },
-      [&](dim3 blocks) {
-        hipLaunchKernelGGL(correct_finalize_kernel, blocks, dim3(256), 0, stream, a.loc.acc,
-                           a.loc.n_stripes, a.loc.k + a.loc.p, status, changed, counts);
-      });
+  return cor_launch(a, loc_flat_aligned(a.loc), list, n_list, status, changed, counts, stream);
 }
 
 hipError_t launch_correct(const CorrectArgs& args, uint8_t* status, uint8_t* changed,
                           uint32_t* counts, hipStream_t stream) {
-  static_assert(kCorAccBad == kCorAccStored + 2 && kCorAccSkipped < kLocAccWords, "accumulator");
   CorrectArgs a = args;
-  return loc_launch(
-      a.loc, stream,
-      [&](auto no, auto multi, dim3 grid) {
-        hipLaunchKernelGGL((correct_kernel<decltype(no)::value, decltype(multi)::value>), grid,
-                           dim3(kLocBlock), 0, stream, a);
-      },
-      [&](dim3 blocks) {
-        hipLaunchKernelGGL(correct_finalize_kernel, blocks, dim3(256), 0, stream, a.loc.acc,
-                           a.loc.n_stripes, a.loc.k + a.loc.p, status, changed, counts);
-      });
+  return cor_launch(a, loc_flat_aligned(a.loc), nullptr, nullptr, status, changed, counts, stream);
+}
+
+hipError_t launch_correct_shards(const CorrectShardsArgs& args, const uint32_t* list,
+                                 const uint32_t* n_list, uint8_t* status, uint8_t* changed,
+                                 uint32_t* counts, hipStream_t stream) {
+  CorrectShardsArgs a = args;
+  return cor_launch(a, a.vec != 0u, list, n_list, status, changed, counts, stream);
 }
 
 }  // namespace rse

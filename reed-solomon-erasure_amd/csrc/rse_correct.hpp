@@ -19,6 +19,20 @@ struct CorrectArgs {
   const uint8_t* present;  // n_stripes x (k + p), 0 = erased; null: nothing is erased
 };
 
+// rse_scrub_shards' stripes: one pointer per shard, and a stripe is a block of
+// cor.loc.shard_bytes of every shard -- block s of shard r starts at
+// ptr[r] + s * cor.loc.shard_bytes.  cor.loc.base is not used, and
+// cor.loc.n_stripes counts the blocks, the shorter last one included.  The
+// table travels in the kernel arguments (2,040 B of the 4 KiB block): nothing
+// to copy, nothing whose lifetime outlasts the call.
+constexpr uint32_t kCorMaxShards = 255;
+struct CorrectShardsArgs {
+  CorrectArgs cor;
+  uint64_t tail_bytes;  // of the last block where it is shorter than the others, else 0
+  uint32_t vec;         // the 16-byte path: every pointer and the block bytes are multiples of 16
+  const uint8_t* ptr[kCorMaxShards];
+};
+
 // The repairing pass over every stripe, then the pass that turns the
 // accumulators into status (n_stripes), changed (n_stripes x (k + p), nullable)
 // and counts (n_stripes x 2, nullable).
@@ -32,6 +46,12 @@ hipError_t launch_correct(const CorrectArgs& a, uint8_t* status, uint8_t* change
 hipError_t launch_correct_list(const CorrectArgs& a, const uint32_t* list, const uint32_t* n_list,
                                uint8_t* status, uint8_t* changed, uint32_t* counts,
                                hipStream_t stream);
+
+// Both of the above for separately allocated shards: the blocks
+// list[0 .. *n_list), or every block when list is null.
+hipError_t launch_correct_shards(const CorrectShardsArgs& a, const uint32_t* list,
+                                 const uint32_t* n_list, uint8_t* status, uint8_t* changed,
+                                 uint32_t* counts, hipStream_t stream);
 
 // Ascending into list[0 .. *count): the stripes with a nonzero word in `words`
 // (n_stripes), a zero flag in their row of `present` (n_stripes x n) or a

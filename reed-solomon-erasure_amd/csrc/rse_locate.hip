@@ -74,11 +74,12 @@ __global__ __launch_bounds__(kLocBlock) void locate_kernel(const LocateArgs a) {
   const uint8_t* tabs = reinterpret_cast<const uint8_t*>(s_tab);
   const LocLds l{tabs + kLocLogOff, tabs + kLocExpOff, tabs + kLocTOff, s_acc};
   const uint32_t p = a.p, n = a.k + a.p;
-  const auto slow = [&](const auto& acc, const uint8_t*, uint64_t) { loc_slow(l, acc, p, n); };
+  const auto slow = [&](const auto& acc, const LocFlat&, uint64_t) { loc_slow(l, acc, p, n); };
   const uint64_t stride = (uint64_t)(a.k + a.p) * a.shard_bytes;
 
   for (uint64_t stripe = blockIdx.y; stripe < a.n_stripes; stripe += gridDim.y) {
-    loc_sweep<NO, MULTI>(a, tq, tt2, a.base + stripe * stride, slow);
+    loc_sweep<NO, MULTI>(a, tq, tt2, LocFlat{a.base + stripe * stride, a.shard_bytes, a.n_vec},
+                         slow);
     // the workgroup's findings on this stripe, one atomic per touched word
     __syncthreads();
     if (threadIdx.x < 9) {
@@ -122,7 +123,7 @@ hipError_t launch_locate(const LocateArgs& args, uint8_t* present, uint8_t* stat
                          hipStream_t stream) {
   LocateArgs a = args;
   return loc_launch(
-      a, stream,
+      a, loc_flat_aligned(a), stream,
       [&](auto no, auto multi, dim3 grid) {
         hipLaunchKernelGGL((locate_kernel<decltype(no)::value, decltype(multi)::value>), grid,
                            dim3(kLocBlock), 0, stream, a);

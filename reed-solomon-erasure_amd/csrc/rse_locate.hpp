@@ -14,7 +14,8 @@ namespace rse {
 constexpr uint32_t kLocAccWords = 16;
 
 struct LocateArgs {
-  const uint8_t* base;    // stripe 0, shard 0 (flat layout: k + p shards end to end)
+  const uint8_t* base;    // stripe 0, shard 0 (flat layout: k + p shards end to end; not
+                          // used where the shards come as pointers, CorrectShardsArgs)
   uint64_t shard_bytes;
   uint64_t n_vec;         // 16-byte vectors of every shard the vector body takes
   uint64_t n_stripes;

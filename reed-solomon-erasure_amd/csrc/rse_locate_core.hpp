@@ -67,16 +67,55 @@ __device__ __forceinline__ void loc_column_d(const uint32_t (&acc)[NO][NW], uint
   }
 }
 
+// Where the shards of the stripe a workgroup sweeps lie, and how long they
+// are: a layout has shard_bytes, n_vec (the 16-byte vectors of every shard the
+// vector body takes) and from(r0, off), a cursor over the shards from r0 on at
+// byte offset `off` -- cursor(i) is the address of that byte of shard r0 + i.
+//
+// Flat, rse_locate_flat's and rse_correct_flat's: the k + p shards of a stripe
+// end to end from sbase.
+struct LocFlat {
+  const uint8_t* sbase;
+  uint64_t shard_bytes, n_vec;
+  struct Cursor {
+    const uint8_t* p;
+    uint64_t sb;
+    __device__ __forceinline__ const uint8_t* operator()(uint32_t i) const {
+      return p + (uint64_t)i * sb;
+    }
+  };
+  __device__ __forceinline__ Cursor from(uint32_t r0, uint64_t off) const {
+    return Cursor{sbase + (uint64_t)r0 * shard_bytes + off, shard_bytes};
+  }
+};
+
+// One pointer per shard, rse_scrub_shards': the stripe is a block of
+// shard_bytes of every shard, `boff` bytes into it.  The table is read at a
+// wave-uniform index on the fast path (a scalar load) and at the lane's shard
+// on the slow path.
+struct LocPtrs {
+  const uint8_t* const* ptr;
+  uint64_t boff, shard_bytes, n_vec;
+  struct Cursor {
+    const uint8_t* const* q;
+    uint64_t o;
+    __device__ __forceinline__ const uint8_t* operator()(uint32_t i) const { return q[i] + o; }
+  };
+  __device__ __forceinline__ Cursor from(uint32_t r0, uint64_t off) const {
+    return Cursor{ptr + r0, boff + off};
+  }
+};
+
 // One unit of a workgroup's sweep: lane t takes NW words of every shard at
-// byte offset `off` of the stripe at sbase (NW = 4: a 16-byte vector; NW = 1:
+// byte offset `off` of the stripe `lay` (NW = 4: a 16-byte vector; NW = 1:
 // one byte, for the ragged tail and unaligned stripes).  Called by every
 // thread of the workgroup (MULTI rebuilds the tables between barriers).  A
 // wave whose d is zero in every lane is done; in any other, the lanes with a
-// nonzero d call slow(acc, sbase, off) -- the rare path, inlined so that the
+// nonzero d call slow(acc, lay, off) -- the rare path, inlined so that the
 // accumulators are never passed through memory.
-template <int NO, int NW, bool MULTI, class Slow>
+template <int NO, int NW, bool MULTI, class Lay, class Slow>
 __device__ __forceinline__ void loc_unit(const LocateArgs& a, uint4* tq, uint32_t* tt2,
-                                         const uint8_t* sbase, uint64_t off, bool valid,
+                                         const Lay& lay, uint64_t off, bool valid,
                                          const Slow& slow) {
   constexpr uint32_t KCH = loc_tabs<NO>() / NO;
   const uint32_t k = a.k, p = a.p;
@@ -93,12 +132,12 @@ __device__ __forceinline__ void loc_unit(const LocateArgs& a, uint4* tq, uint32_
       __syncthreads();
     }
     const uint32_t lb = opaque_zero();
-    const uint8_t* in = sbase + (uint64_t)c0 * a.shard_bytes + off;
+    const auto in = lay.from(c0, off);
     for (uint32_t i0 = 0; i0 < kc; i0 += kLocKC) {
       uint32_t x[kLocKC][NW];
 #pragma unroll
       for (int j = 0; j < kLocKC; ++j)
-        if (i0 + j < kc) loc_load<NW>(in + (uint64_t)(i0 + j) * a.shard_bytes, valid, x[j]);
+        if (i0 + j < kc) loc_load<NW>(in(i0 + j), valid, x[j]);
 #pragma unroll
       for (int j = 0; j < kLocKC; ++j) {
         if (!(i0 + j < kc)) continue;
@@ -121,12 +160,12 @@ __device__ __forceinline__ void loc_unit(const LocateArgs& a, uint4* tq, uint32_
     }
   }
   uint32_t any = 0u;
-  const uint8_t* par = sbase + (uint64_t)k * a.shard_bytes + off;
+  const auto par = lay.from(k, off);
 #pragma unroll
   for (int r = 0; r < NO; ++r) {
     if (!((uint32_t)r < p)) continue;
     uint32_t x[NW];
-    loc_load<NW>(par + (uint64_t)r * a.shard_bytes, valid, x);
+    loc_load<NW>(par((uint32_t)r), valid, x);
 #pragma unroll
     for (int w = 0; w < NW; ++w) {
       acc[r][w] ^= x[w];
@@ -134,7 +173,7 @@ __device__ __forceinline__ void loc_unit(const LocateArgs& a, uint4* tq, uint32_
     }
   }
   if (__ballot(any != 0u) == 0ull) return;
-  if (any != 0u) slow(acc, sbase, off);
+  if (any != 0u) slow(acc, lay, off);
 }
 
 // Units of 256 lanes in a stripe's sweep: the 16-byte vectors, then the
@@ -154,31 +193,35 @@ struct LocGridPart {
 
 // The sweep of one stripe by one workgroup: its units of 256 lanes, 16-byte
 // vectors first, then the byte-wise part.
-template <int NO, bool MULTI, class Slow, class Part = LocGridPart>
+template <int NO, bool MULTI, class Lay, class Slow, class Part = LocGridPart>
 __device__ __forceinline__ void loc_sweep(const LocateArgs& a, uint4* tq, uint32_t* tt2,
-                                          const uint8_t* sbase, const Slow& slow,
+                                          const Lay& lay, const Slow& slow,
                                           const Part& part = Part{}) {
-  const uint64_t n_vspans = (a.n_vec + kLocBlock - 1) / kLocBlock;
-  const uint64_t tail0 = a.n_vec * 16u;  // first byte of the byte-wise part
-  const uint64_t n_units = n_vspans + (a.shard_bytes - tail0 + kLocBlock - 1) / kLocBlock;
+  const uint64_t n_vspans = (lay.n_vec + kLocBlock - 1) / kLocBlock;
+  const uint64_t tail0 = lay.n_vec * 16u;  // first byte of the byte-wise part
+  const uint64_t n_units = n_vspans + (lay.shard_bytes - tail0 + kLocBlock - 1) / kLocBlock;
   for (uint64_t u = part.first(); u < n_units; u += part.step()) {
     if (u < n_vspans) {
       const uint64_t v = u * kLocBlock + threadIdx.x;
-      loc_unit<NO, 4, MULTI>(a, tq, tt2, sbase, v * 16u, v < a.n_vec, slow);
+      loc_unit<NO, 4, MULTI>(a, tq, tt2, lay, v * 16u, v < lay.n_vec, slow);
     } else {
       const uint64_t b = tail0 + (u - n_vspans) * kLocBlock + threadIdx.x;
-      loc_unit<NO, 1, MULTI>(a, tq, tt2, sbase, b, b < a.shard_bytes, slow);
+      loc_unit<NO, 1, MULTI>(a, tq, tt2, lay, b, b < lay.shard_bytes, slow);
     }
   }
 }
 
+// Does every shard of the flat layout start on a 16-byte boundary?
+inline bool loc_flat_aligned(const LocateArgs& a) {
+  return (reinterpret_cast<uintptr_t>(a.base) % 16u) == 0 && a.shard_bytes % 16u == 0;
+}
+
 // Vector width and grid of both passes.  16-byte vectors when every shard
-// starts on a 16-byte boundary.  A few workgroups per CU over the whole grid,
+// starts on a 16-byte boundary (al).  A few workgroups per CU over the whole grid,
 // and at most four units per workgroup while that keeps the grid small: the
 // stripes that take the slow path are then spread over many CUs instead of
 // trailing the clean ones on eight workgroups each.
-inline dim3 loc_grid(LocateArgs& a) {
-  const bool al = (reinterpret_cast<uintptr_t>(a.base) % 16u) == 0 && a.shard_bytes % 16u == 0;
+inline dim3 loc_grid(LocateArgs& a, bool al) {
   a.n_vec = al ? a.shard_bytes / 16u : 0;
   const uint64_t units = (a.n_vec + kLocBlock - 1) / kLocBlock +
                          (a.shard_bytes - a.n_vec * 16u + kLocBlock - 1) / kLocBlock;
@@ -195,15 +238,15 @@ inline dim3 loc_grid(LocateArgs& a) {
 // kernel, the finalize kernel.  sweep(NO, MULTI, grid) launches the caller's
 // sweep kernel for these two integral constants; finalize(blocks) launches its
 // finalize kernel, one thread per (stripe, shard) up to 65536 blocks.  Sets
-// a.n_vec (loc_grid), which the sweep kernel reads.
+// a.n_vec (loc_grid, by `al`), which the sweep kernel reads.
 template <class Sweep, class Finalize>
-hipError_t loc_launch(LocateArgs& a, hipStream_t stream, const Sweep& sweep,
+hipError_t loc_launch(LocateArgs& a, bool al, hipStream_t stream, const Sweep& sweep,
                       const Finalize& finalize) {
   if (!locate_in_scope(8, a.k, a.p) || a.shard_bytes == 0 || a.n_stripes == 0)
     return hipErrorInvalidValue;
   hipError_t e = hipMemsetAsync(a.acc, 0, a.n_stripes * kLocAccWords * sizeof(uint32_t), stream);
   if (e != hipSuccess) return e;
-  const dim3 grid = loc_grid(a);
+  const dim3 grid = loc_grid(a, al);
   const auto with_no = [&](auto no) {
     constexpr int NO = decltype(no)::value;
     constexpr uint32_t KCH = loc_tabs<NO>() / NO;

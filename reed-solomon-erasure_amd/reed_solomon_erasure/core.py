@@ -457,6 +457,43 @@ class ReedSolomon:
         return (status[:n_stripes], changed[:n_stripes], counts[:n_stripes],
                 bad_stripes[:n_stripes], n_bad)
 
+    def scrub(self, shards: ShardList, block_len: Optional[int] = None, present=None
+              ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+        """scrub_flat() for separately allocated shards (rse_scrub_shards):
+        ``shards`` is a sequence of k + p contiguous 1-D device tensors on one
+        device, as encode() takes them -- the rows of a ``[k, L]`` and a
+        ``[p, L]`` tensor, say -- repaired in place.  The results are per
+        block of ``block_len`` elements of every shard (None or 0: one block,
+        the whole shard; the last block may be shorter): ``(status, changed,
+        counts, bad_blocks, n_bad)`` as scrub_flat() returns them with a row
+        per block, ``n_blocks = ceil(len / min(block_len, len))``.  ``present``
+        as in scrub_flat(), ``n_blocks x (k+p)``.  Queued on the current
+        stream, no synchronisation.  Same codecs as scrub_flat()."""
+        T = self.total_shard_count()
+        if len(shards) == 0:
+            raise RSError(Error.TooFewShards)
+        ptrs, lens = _arrays(shards, self.field)
+        first = _first(shards)
+        if any(s.device != first.device for s in shards):
+            raise ValueError("shards must be on one device")
+        length = lens[0] if len(shards) else 0
+        block = min(block_len or length, length)
+        n_blocks = -(-length // block) if block else 0
+        pres = _stripe_flags(present, first, n_blocks, T)
+        # at least one row: an empty tensor has no address to pass
+        rows = max(1, n_blocks)
+        status = torch.empty((rows,), dtype=torch.uint8, device=first.device)
+        changed = torch.empty((rows, T), dtype=torch.uint8, device=first.device)
+        counts = torch.empty((rows, 2), dtype=torch.int32, device=first.device)
+        bad_blocks = torch.empty((rows,), dtype=torch.int32, device=first.device)
+        n_bad = torch.zeros((1,), dtype=torch.int32, device=first.device)
+        _raise(_lib.rse_scrub_shards(self._h, ptrs, lens, len(shards), block_len or 0,
+                                     pres.data_ptr() if pres is not None and n_blocks else None,
+                                     status.data_ptr(), changed.data_ptr(), counts.data_ptr(),
+                                     bad_blocks.data_ptr(), n_bad.data_ptr(), _stream(first)))
+        return (status[:n_blocks], changed[:n_blocks], counts[:n_blocks],
+                bad_blocks[:n_blocks], n_bad)
+
     def reconstruct_data_flat(self, stripes: torch.Tensor, shard_len: int, n_stripes: int,
                               present: Sequence[bool]) -> None:
         """wasm/src/lib.rs:57-73 over many stripes sharing one erasure pattern."""
