@@ -32,6 +32,8 @@
 #include "rse_fft16.hpp"
 #include "rse_correct.hpp"
 #include "rse_scrub_shards_plan.hpp"
+#include "rse_update.hpp"
+#include "rse_update_plan.hpp"
 #include "rse_correct_plan.hpp"
 #include "rse_locate.hpp"
 #include "rse_locate_plan.hpp"
@@ -142,6 +144,9 @@ struct rse_codec {
   // Per device: rse_locate_flat's plan (rse_locate_plan.hpp locate_consts),
   // made on the first locate there and kept likewise (locate_plan_consts).
   mutable DevConsts locate_dev;
+  // Per device: rse_update_flat's parity rows, p x k bytes (in scope the
+  // coefficients are below 256), made on the first update there (update_consts).
+  mutable DevConsts update_dev;
 
   size_t esize() const { return field == 16 ? 2 : 1; }
   uint16_t mat(size_t r, size_t c) const { return field == 16 ? m16.at(r, c) : m8.at(r, c); }
@@ -798,6 +803,15 @@ hipError_t locate_plan_consts(const rse_codec* c, int dev, const uint8_t** out) 
     std::vector<uint8_t> h(rse::kCorConstsBytes, 0);
     rse::correct_consts(pl, h.data());
     return h;
+  }, out);
+}
+
+// The codec's parity rows as bytes on device `dev` (rse_codec::update_dev; the
+// first rse_update_flat there pays the copy).
+hipError_t update_consts(const rse_codec* c, int dev, const uint8_t** out) {
+  return c->update_dev.get(dev, [c] {
+    const Rows r = parity_rows(c);
+    return std::vector<uint8_t>(r.c.begin(), r.c.end());  // update_in_scope: each below 256
   }, out);
 }
 
@@ -2657,6 +2671,48 @@ int rse_scrub_shards(const rse_codec* c, void* const* shards, const size_t* lens
     rse::note_kernel("scrub-shards gf%d %zu+%zu %s", c->field, c->k, c->p,
                      pre ? "prefilter" : "direct");
   return rc;
+}
+
+// Data shards rewritten and the parity patched by the delta (rse_update.hip):
+// the plan kernel over the list, then the update kernel, which a rejected list
+// stops.  The workspace -- the verdict, the run count, a run head per entry at
+// most -- is the call's own.
+int rse_update_flat(const rse_codec* c, void* stripes, size_t shard_len, size_t n_stripes,
+                    const uint32_t* updates, const void* new_data, size_t n_updates,
+                    uint32_t* result, rse_stream_t stream) {
+  if (!c || !stripes || !updates || !new_data || !result) return RSE_ERR_INVALID_ARGUMENT;
+  if (!rse::update_in_scope(c->field, c->k, c->p)) return RSE_ERR_INVALID_ARGUMENT;
+  if (shard_len == 0) return RSE_EMPTY_SHARD;
+  if (n_updates == 0) return RSE_OK;
+  if (n_stripes == 0 || n_stripes > 0xffffffffu || n_updates > 0xffffffffu)
+    return RSE_ERR_INVALID_ARGUMENT;
+  RSE_ON_STREAM(stream);
+  hipStream_t st = (hipStream_t)stream;
+  int dev = 0, cus = 0;
+  RSE_HIP(hipGetDevice(&dev));
+  RSE_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+  rse::UpdateArgs a{};
+  RSE_HIP(update_consts(c, dev, &a.coef));
+  a.base = static_cast<uint8_t*>(stripes);
+  a.shard_bytes = shard_len * c->esize();
+  a.n_stripes = (uint32_t)n_stripes;
+  a.k = (uint32_t)c->k;
+  a.p = (uint32_t)c->p;
+  a.n_updates = (uint32_t)n_updates;
+  a.updates = updates;
+  a.new_data = static_cast<const uint8_t*>(new_data);
+  a.result = result;
+  a.vec = rse::update_vec(stripes, new_data, a.shard_bytes) ? 1u : 0u;
+  const uint32_t grid = rse::update_grid((uint32_t)cus, rse::get_option(RSE_OPT_GRID_X), n_updates,
+                                         a.shard_bytes);
+  RSE_HIP(hipMallocAsync(reinterpret_cast<void**>(&a.ws),
+                         (rse::kUpdWsList + n_updates) * sizeof(uint32_t), st));
+  const hipError_t e = rse::launch_update(a, grid, st);
+  const hipError_t f = hipFreeAsync(a.ws, st);
+  if (e != hipSuccess) return dev_fail(e);
+  if (f != hipSuccess) return dev_fail(f);
+  rse::note_kernel("update gf%d %zu+%zu %s", c->field, c->k, c->p, a.vec ? "vec" : "bytes");
+  return RSE_OK;
 }
 
 int rse_reconstruct_data_flat(const rse_codec* c, void* stripes, size_t shard_len,

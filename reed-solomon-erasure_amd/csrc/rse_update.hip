@@ -1,0 +1,210 @@
+// rse_update.hip -- rse_update_flat: data shards rewritten in place and the
+// parity patched by the delta, parity_j ^= M[k+j][i] * (old_i ^ new_i)
+// (encode_single's accumulation, core.rs:545-562, applied to a difference).
+//
+// Two launches on the caller's stream.  update_plan_kernel, one workgroup,
+// walks the list once: the in-order predicate of every entry
+// (rse_update_plan.hpp) with the lowest offender kept, the run heads compacted
+// in ascending order into the workspace, the verdict into the workspace and
+// into the caller's `result`.  update_kernel exits at once on a rejected list
+// -- no address is ever formed from an entry that is not in order -- and else
+// steps in grid strides over (run, span) items: one stripe's entries, 4 KiB of
+// every shard they name, 16 bytes per lane.  The list is strictly ascending,
+// so a run is its stripe's only writer: no atomics on shard bytes.
+//
+// Per item the lane loads its 16 bytes of every parity row of the group into
+// the accumulators, then for every entry of the run loads old and new, stores
+// new over old (same lane, same address), and adds M[k+r][shard] * (old ^ new)
+// to every row with the table multiply of rse_kernels.hip (gf8_mac4); then the
+// rows are stored.  The tables of a group's rows x k coefficients are built
+// per workgroup into LDS from the codec's parity rows on the device.  More
+// than kUpdRows parity rows are taken group by group, the groups outermost so
+// that a workgroup builds each group's tables once: an item is always the same
+// workgroup's and lane's, which re-reads old and new in every group's pass and
+// stores the data shard in the last one, so every pass sees the old bytes.
+//
+// A GF(2^16) codec of at most 256 shards has its coefficients in the GF(2^8)
+// subfield, where a constant multiplies each byte of an element by itself
+// (rse_codec::kfield): the same kernel over 2 x shard_len bytes.
+#include "rse_update.hpp"
+
+#include "rse_device.hpp"
+#include "rse_update_plan.hpp"
+
+namespace rse {
+namespace {
+
+constexpr int kPlanBlock = 1024, kPlanWaves = kPlanBlock / 64;
+constexpr uint32_t kNoOffender = 0xFFFFFFFFu;  // n_updates <= 2^32 - 1: no entry has this index
+
+__global__ __launch_bounds__(kPlanBlock) void update_plan_kernel(UpdateArgs a) {
+  __shared__ uint32_t s_wave[2][kPlanWaves];
+  __shared__ uint32_t s_bad;
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  if (threadIdx.x == 0) s_bad = kNoOffender;
+  uint32_t bad = kNoOffender, base = 0u;
+  // a head's place in the list: the heads of the trips before (base), of the
+  // waves before (through LDS, two buffers so that a trip needs one barrier)
+  // and of the lanes below
+  for (uint64_t u0 = 0, trip = 0; u0 < a.n_updates; u0 += kPlanBlock, ++trip) {
+    const uint64_t u = u0 + threadIdx.x;
+    bool head = false;
+    if (u < a.n_updates) {
+      if (bad == kNoOffender && !update_in_order(a.updates, u, a.n_stripes, a.k)) bad = (uint32_t)u;
+      head = update_run_head(a.updates, u);
+    }
+    const unsigned long long heads = __ballot(head);
+    if (lane == 0) s_wave[trip & 1u][wave] = (uint32_t)__popcll(heads);
+    __syncthreads();
+    uint32_t at = base;
+#pragma unroll
+    for (int w = 0; w < kPlanWaves; ++w) {
+      const uint32_t v = s_wave[trip & 1u][w];
+      base += v;
+      if ((uint32_t)w < wave) at += v;
+    }
+    if (head)
+      a.ws[kUpdWsList + at + (uint32_t)__popcll(heads & ((1ull << lane) - 1ull))] = (uint32_t)u;
+  }
+  if (bad != kNoOffender) atomicMin(&s_bad, bad);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const uint32_t first = s_bad;
+    const bool rejected = first != kNoOffender;
+    a.ws[kUpdWsStatus] = rejected ? RSE_UPDATE_REJECTED : RSE_UPDATE_APPLIED;
+    a.ws[kUpdWsRuns] = base;
+    a.result[0] = rejected ? RSE_UPDATE_REJECTED : RSE_UPDATE_APPLIED;
+    a.result[1] = rejected ? first : base;  // accepted: a run per touched stripe
+  }
+}
+
+// A lane's n <= 16 bytes at p: one 16-byte access on the vector path (n is 16
+// there), byte by byte otherwise, the bytes past n read as zero and not stored.
+template <bool VEC>
+__device__ __forceinline__ uint4 ld_lane(const uint8_t* p, uint32_t n) {
+  if constexpr (VEC) {
+    return ld16(p);
+  } else {
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (uint32_t b = 0; b < kUpdLaneBytes; ++b)
+      if (b < n) w[b / 4] |= (uint32_t)((gptr<const uint8_t>)p)[b] << (8u * (b % 4));
+    return make_uint4(w[0], w[1], w[2], w[3]);
+  }
+}
+template <bool VEC>
+__device__ __forceinline__ void st_lane(uint8_t* p, uint4 v, uint32_t n) {
+  if constexpr (VEC) {
+    st16(p, v);
+  } else {
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (uint32_t b = 0; b < kUpdLaneBytes; ++b)
+      if (b < n) ((gptr<uint8_t>)p)[b] = (uint8_t)(w[b / 4] >> (8u * (b % 4)));
+  }
+}
+
+// TABS: tables the LDS image holds, at least group rows x k.  NO: parity rows
+// a lane accumulates, at least the group's.
+template <int TABS, int NO, bool VEC>
+__global__ __launch_bounds__(kUpdBlock) void update_kernel(UpdateArgs a) {
+  __shared__ uint4 tq[TABS];
+  __shared__ uint32_t tt2[TABS];
+  if (a.ws[kUpdWsStatus] != RSE_UPDATE_APPLIED) return;  // rejected: nothing is read or written
+
+  const uint32_t k = a.k, p = a.p, n_updates = a.n_updates;
+  const uint64_t bytes = a.shard_bytes;
+  const uint64_t n_spans = update_spans(bytes);
+  const uint64_t n_items = (uint64_t)a.ws[kUpdWsRuns] * n_spans;
+  const uint32_t n_groups = update_row_groups(p);
+
+  for (uint32_t g = 0; g < n_groups; ++g) {
+    const uint32_t row0 = update_group_first(g), rows = update_group_rows(p, g);
+    const bool last = g + 1 == n_groups;
+    if (g != 0) __syncthreads();  // the group before is done with its tables
+    // table (r, i) of the group at index r * k + i
+    for (uint32_t t = threadIdx.x; t < rows * k; t += kUpdBlock)
+      write_tab(tq, tt2, t, make_gf8_tab(a.coef[(size_t)row0 * k + t]));
+    __syncthreads();
+
+    for (uint64_t item = blockIdx.x; item < n_items; item += gridDim.x) {
+      const uint64_t run = item / n_spans, span = item % n_spans;
+      const uint32_t head = __builtin_amdgcn_readfirstlane(a.ws[kUpdWsList + run]);
+      const uint32_t stripe = __builtin_amdgcn_readfirstlane(a.updates[2 * (uint64_t)head]);
+      const uint32_t n = update_lane_len(update_span_len(bytes, span), threadIdx.x);
+      if (n == 0) continue;  // no barrier below: the lanes past the shard's end sit the item out
+      const uint64_t off = update_span_first(span) + (uint64_t)threadIdx.x * kUpdLaneBytes;
+      uint8_t* const sbase = a.base + (uint64_t)stripe * (k + p) * bytes + off;
+      uint8_t* const par = sbase + (uint64_t)(k + row0) * bytes;
+
+      uint4 acc[NO];
+#pragma unroll
+      for (int r = 0; r < NO; ++r) {
+        acc[r] = make_uint4(0u, 0u, 0u, 0u);
+        if ((uint32_t)r < rows) acc[r] = ld_lane<VEC>(par + (uint64_t)r * bytes, n);
+      }
+      for (uint32_t e = head; e < n_updates; ++e) {
+        if (__builtin_amdgcn_readfirstlane(a.updates[2 * (uint64_t)e]) != stripe) break;
+        const uint32_t shard = __builtin_amdgcn_readfirstlane(a.updates[2 * (uint64_t)e + 1]);
+        uint8_t* const dst = sbase + (uint64_t)shard * bytes;
+        const uint4 old = ld_lane<VEC>(dst, n);
+        const uint4 nw = ld_lane<VEC>(a.new_data + (uint64_t)e * bytes + off, n);
+        if (last) st_lane<VEC>(dst, nw, n);
+        const Sel s0 = make_sel(old.x ^ nw.x), s1 = make_sel(old.y ^ nw.y),
+                  s2 = make_sel(old.z ^ nw.z), s3 = make_sel(old.w ^ nw.w);
+        // an opaque LDS offset made anew for every entry, and the sums pinned
+        // after it: rse_kernels.hip gf8_span says why
+        const uint32_t lb = opaque_zero();
+#pragma unroll
+        for (int r = 0; r < NO; ++r) {
+          if (!((uint32_t)r < rows)) continue;
+          const Gf8Tab t = read_tab(tq, tt2, lb + r * k + shard);
+          acc[r].x = gf8_mac4(acc[r].x, t, s0);
+          acc[r].y = gf8_mac4(acc[r].y, t, s1);
+          acc[r].z = gf8_mac4(acc[r].z, t, s2);
+          acc[r].w = gf8_mac4(acc[r].w, t, s3);
+        }
+#pragma unroll
+        for (int r = 0; r < NO; ++r) pin(acc[r]);
+      }
+#pragma unroll
+      for (int r = 0; r < NO; ++r)
+        if ((uint32_t)r < rows) st_lane<VEC>(par + (uint64_t)r * bytes, acc[r], n);
+    }
+  }
+}
+
+template <int TABS, int NO>
+void launch_one(const UpdateArgs& a, uint32_t grid, hipStream_t stream) {
+  if (a.vec != 0u)
+    hipLaunchKernelGGL((update_kernel<TABS, NO, true>), dim3(grid), dim3(kUpdBlock), 0, stream, a);
+  else
+    hipLaunchKernelGGL((update_kernel<TABS, NO, false>), dim3(grid), dim3(kUpdBlock), 0, stream, a);
+}
+
+// LDS images: the small one keeps eight workgroups on a compute unit, the
+// large one (a group of 16 rows of a codec with k up to 255) one or two.
+constexpr int kTabsSmall = 1024, kTabsLarge = 4096;
+
+}  // namespace
+
+hipError_t launch_update(const UpdateArgs& a, uint32_t grid, hipStream_t stream) {
+  if (a.k == 0 || a.p == 0 || a.k + a.p > 256 || a.shard_bytes == 0 || a.n_stripes == 0 ||
+      a.n_updates == 0 || grid == 0)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(update_plan_kernel, dim3(1), dim3(kPlanBlock), 0, stream, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  const uint32_t rows = a.p < kUpdRows ? a.p : kUpdRows;  // of the largest group
+  if (rows * a.k > (uint32_t)kTabsSmall)
+    launch_one<kTabsLarge, 16>(a, grid, stream);
+  else if (rows <= 4)
+    launch_one<kTabsSmall, 4>(a, grid, stream);
+  else if (rows <= 8)
+    launch_one<kTabsSmall, 8>(a, grid, stream);
+  else
+    launch_one<kTabsSmall, 16>(a, grid, stream);
+  return hipGetLastError();
+}
+
+}  // namespace rse

@@ -17,9 +17,11 @@ _load()  # fail at import time, loudly, if the HIP library is missing
 from .core import ReedSolomon, ShardByShard  # noqa: E402
 from .core import LOCATE_CLEAN, LOCATE_LOCATED, LOCATE_UNCORRECTABLE  # noqa: E402
 from .core import CORRECT_CLEAN, CORRECT_CORRECTED, CORRECT_UNCORRECTABLE  # noqa: E402
+from .core import UPDATE_APPLIED, UPDATE_REJECTED  # noqa: E402
 from . import galois_8, galois_16  # noqa: E402
 
 __all__ = ["ReedSolomon", "ShardByShard", "Error", "RSError", "SBSError", "SBSErrorKind",
            "DeviceError", "galois_8", "galois_16",
            "LOCATE_CLEAN", "LOCATE_LOCATED", "LOCATE_UNCORRECTABLE",
-           "CORRECT_CLEAN", "CORRECT_CORRECTED", "CORRECT_UNCORRECTABLE"]
+           "CORRECT_CLEAN", "CORRECT_CORRECTED", "CORRECT_UNCORRECTABLE",
+           "UPDATE_APPLIED", "UPDATE_REJECTED"]

@@ -26,6 +26,9 @@ LOCATE_UNCORRECTABLE = 2
 CORRECT_CLEAN = 0
 CORRECT_CORRECTED = 1
 CORRECT_UNCORRECTABLE = 2
+# rse_update_flat's result[0] (RSE_UPDATE_*)
+UPDATE_APPLIED = 0
+UPDATE_REJECTED = 1
 
 ShardList = Sequence[torch.Tensor]
 
@@ -493,6 +496,57 @@ class ReedSolomon:
                                      bad_blocks.data_ptr(), n_bad.data_ptr(), _stream(first)))
         return (status[:n_blocks], changed[:n_blocks], counts[:n_blocks],
                 bad_blocks[:n_blocks], n_bad)
+
+    def update_flat(self, stripes: torch.Tensor, shard_len: int, n_stripes: int, updates,
+                    new_data: torch.Tensor) -> torch.Tensor:
+        """Rewrite data shards of the flat layout in place and patch the parity
+        by the delta (rse_update_flat).  ``updates`` is an ``(n, 2)``
+        int32/uint32 array of ``{stripe, data shard}`` rows in strictly
+        ascending order -- a host array is uploaded, a device tensor is read in
+        place -- and ``new_data`` a uint8 device tensor of ``n x shard_len``
+        elements, row u the new contents of entry u; it must not overlap
+        ``stripes``.  Returns the ``(2,)`` int32 device tensor ``result``:
+        ``{UPDATE_APPLIED, stripes touched}``, or ``{UPDATE_REJECTED, index of
+        the first entry out of order}`` with nothing written.  Each touched
+        stripe keeps its syndrome: one that verified still verifies, one with
+        latent corruption stays as repairable by scrub_flat() as it was.
+        Queued on the current stream, no synchronisation: ``result`` is read
+        by whoever needs it, after synchronising.  Every galois_8 codec;
+        galois_16 codecs with k + p <= 256."""
+        T = self.total_shard_count()
+        _check_flat(stripes, shard_len, n_stripes, T, self.field)
+        base = _dev(stripes)
+        if isinstance(updates, torch.Tensor) and updates.is_cuda:
+            upd = updates  # read in place, on that device
+        else:
+            rows = np.asarray(updates.cpu() if isinstance(updates, torch.Tensor) else updates)
+            if rows.size and (rows.min() < 0 or rows.max() > 0xFFFFFFFF):
+                raise ValueError("updates must hold unsigned 32-bit values")
+            if rows.size == 0:
+                rows = rows.reshape(0, 2)
+            if rows.ndim != 2 or rows.shape[1] != 2:
+                raise ValueError("updates must have shape (n, 2)")
+            rows = np.ascontiguousarray(rows.astype(np.uint32)).view(np.int32)
+            upd = torch.from_numpy(rows).to(stripes.device)
+        if (upd.dim() != 2 or upd.shape[1] != 2 or not upd.is_contiguous()
+                or upd.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32))
+                or upd.device != stripes.device):
+            raise ValueError("updates must be a contiguous (n, 2) int32/uint32 array on the "
+                             "stripes' device")
+        n = upd.shape[0]
+        if new_data.dtype != torch.uint8 or not new_data.is_contiguous():
+            raise ValueError("new_data must be a contiguous uint8 tensor")
+        if new_data.device != stripes.device:
+            raise ValueError("new_data must be on the stripes' device")
+        need = n * shard_len * (self.field // 8)
+        if new_data.numel() < need:
+            raise ValueError(f"new_data holds {new_data.numel()} bytes, {need} needed")
+        result = torch.zeros((2,), dtype=torch.int32, device=stripes.device)
+        _raise(_lib.rse_update_flat(self._h, base, shard_len, n_stripes,
+                                    upd.data_ptr() if n else result.data_ptr(),
+                                    _dev(new_data) if need else result.data_ptr(), n,
+                                    result.data_ptr(), _stream(stripes)))
+        return result
 
     def reconstruct_data_flat(self, stripes: torch.Tensor, shard_len: int, n_stripes: int,
                               present: Sequence[bool]) -> None:
