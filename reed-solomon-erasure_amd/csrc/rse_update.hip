@@ -26,6 +26,10 @@
 // A GF(2^16) codec of at most 256 shards has its coefficients in the GF(2^8)
 // subfield, where a constant multiplies each byte of an element by itself
 // (rse_codec::kfield): the same kernel over 2 x shard_len bytes.
+//
+// rse_update_shards is the same two launches with another address rule for
+// update_kernel (UpdShards below): one pointer per shard from the kernel
+// arguments, a block of columns in the place of a stripe, a shorter last block.
 #include "rse_update.hpp"
 
 #include "rse_device.hpp"
@@ -104,12 +108,69 @@ __device__ __forceinline__ void st_lane(uint8_t* p, uint4 v, uint32_t n) {
   }
 }
 
+// Where an item's bytes lie: the addressing policy of update_kernel.  A layout
+// names the call's argument block, says how many bytes span s of a run has (0:
+// the item is sat out), and makes a cursor per item for the lane's offset `off`
+// into the run's stripe: the lane's address in data shard i, and in parity row
+// r of the group whose first row is row0.
+//
+// The flat layout: base + stripe x (k + p) x bytes + shard x bytes.
+struct UpdFlat {
+  using Args = UpdateArgs;
+  static __host__ __device__ __forceinline__ const UpdateArgs& upd(const Args& a) { return a; }
+  static __device__ __forceinline__ uint64_t span_len(const Args& a, uint32_t, uint64_t span) {
+    return update_span_len(a.shard_bytes, span);
+  }
+  struct At {
+    uint8_t *sbase, *par;
+    uint64_t bytes;
+    __device__ __forceinline__ uint8_t* data(uint32_t i) const { return sbase + (uint64_t)i * bytes; }
+    __device__ __forceinline__ uint8_t* row(uint32_t r) const { return par + (uint64_t)r * bytes; }
+  };
+  static __device__ __forceinline__ At at(const Args& a, uint32_t stripe, uint64_t off,
+                                          uint32_t row0) {
+    const uint64_t bytes = a.shard_bytes;
+    uint8_t* const sbase = a.base + (uint64_t)stripe * (a.k + a.p) * bytes + off;
+    return At{sbase, sbase + (uint64_t)(a.k + row0) * bytes, bytes};
+  }
+};
+
+// Separately allocated shards (rse_update_shards): ptr[shard] + block x block
+// bytes, the pointers read from the kernel arguments.  Shard and row indices are
+// the same in every lane, so a pointer is a scalar load.  A run in the shorter
+// last block has the tail's bytes: fewer spans, a shorter last lane.
+struct UpdShards {
+  using Args = UpdateShardsArgs;
+  static __host__ __device__ __forceinline__ const UpdateArgs& upd(const Args& a) {
+    return a.upd;
+  }
+  static __device__ __forceinline__ uint64_t span_len(const Args& a, uint32_t block,
+                                                      uint64_t span) {
+    return update_run_span_len(
+        update_run_bytes(a.upd.shard_bytes, a.tail_bytes, a.n_full, block), span);
+  }
+  struct At {
+    uint8_t* const* ptr;
+    uint64_t o;
+    uint32_t par0;
+    __device__ __forceinline__ uint8_t* data(uint32_t i) const { return ptr[i] + o; }
+    __device__ __forceinline__ uint8_t* row(uint32_t r) const { return ptr[par0 + r] + o; }
+  };
+  static __device__ __forceinline__ At at(const Args& a, uint32_t block, uint64_t off,
+                                          uint32_t row0) {
+    return At{a.ptr, (uint64_t)block * a.upd.shard_bytes + off, a.upd.k + row0};
+  }
+};
+
 // TABS: tables the LDS image holds, at least group rows x k.  NO: parity rows
-// a lane accumulates, at least the group's.
-template <int TABS, int NO, bool VEC>
-__global__ __launch_bounds__(kUpdBlock) void update_kernel(UpdateArgs a) {
+// a lane accumulates, at least the group's.  LAY: UpdFlat or UpdShards; below,
+// "stripe" and "shard bytes" are a block and a full block's bytes for the
+// latter.
+template <int TABS, int NO, bool VEC, class LAY>
+__global__ __launch_bounds__(kUpdBlock) void update_kernel(typename LAY::Args args) {
   __shared__ uint4 tq[TABS];
   __shared__ uint32_t tt2[TABS];
+  const UpdateArgs& a = LAY::upd(args);
   if (a.ws[kUpdWsStatus] != RSE_UPDATE_APPLIED) return;  // rejected: nothing is read or written
 
   const uint32_t k = a.k, p = a.p, n_updates = a.n_updates;
@@ -131,22 +192,21 @@ __global__ __launch_bounds__(kUpdBlock) void update_kernel(UpdateArgs a) {
       const uint64_t run = item / n_spans, span = item % n_spans;
       const uint32_t head = __builtin_amdgcn_readfirstlane(a.ws[kUpdWsList + run]);
       const uint32_t stripe = __builtin_amdgcn_readfirstlane(a.updates[2 * (uint64_t)head]);
-      const uint32_t n = update_lane_len(update_span_len(bytes, span), threadIdx.x);
+      const uint32_t n = update_lane_len(LAY::span_len(args, stripe, span), threadIdx.x);
       if (n == 0) continue;  // no barrier below: the lanes past the shard's end sit the item out
       const uint64_t off = update_span_first(span) + (uint64_t)threadIdx.x * kUpdLaneBytes;
-      uint8_t* const sbase = a.base + (uint64_t)stripe * (k + p) * bytes + off;
-      uint8_t* const par = sbase + (uint64_t)(k + row0) * bytes;
+      const typename LAY::At at = LAY::at(args, stripe, off, row0);
 
       uint4 acc[NO];
 #pragma unroll
       for (int r = 0; r < NO; ++r) {
         acc[r] = make_uint4(0u, 0u, 0u, 0u);
-        if ((uint32_t)r < rows) acc[r] = ld_lane<VEC>(par + (uint64_t)r * bytes, n);
+        if ((uint32_t)r < rows) acc[r] = ld_lane<VEC>(at.row(r), n);
       }
       for (uint32_t e = head; e < n_updates; ++e) {
         if (__builtin_amdgcn_readfirstlane(a.updates[2 * (uint64_t)e]) != stripe) break;
         const uint32_t shard = __builtin_amdgcn_readfirstlane(a.updates[2 * (uint64_t)e + 1]);
-        uint8_t* const dst = sbase + (uint64_t)shard * bytes;
+        uint8_t* const dst = at.data(shard);
         const uint4 old = ld_lane<VEC>(dst, n);
         const uint4 nw = ld_lane<VEC>(a.new_data + (uint64_t)e * bytes + off, n);
         if (last) st_lane<VEC>(dst, nw, n);
@@ -169,26 +229,29 @@ __global__ __launch_bounds__(kUpdBlock) void update_kernel(UpdateArgs a) {
       }
 #pragma unroll
       for (int r = 0; r < NO; ++r)
-        if ((uint32_t)r < rows) st_lane<VEC>(par + (uint64_t)r * bytes, acc[r], n);
+        if ((uint32_t)r < rows) st_lane<VEC>(at.row(r), acc[r], n);
     }
   }
 }
 
-template <int TABS, int NO>
-void launch_one(const UpdateArgs& a, uint32_t grid, hipStream_t stream) {
-  if (a.vec != 0u)
-    hipLaunchKernelGGL((update_kernel<TABS, NO, true>), dim3(grid), dim3(kUpdBlock), 0, stream, a);
+template <int TABS, int NO, class LAY>
+void launch_one(const typename LAY::Args& args, uint32_t grid, hipStream_t stream) {
+  if (LAY::upd(args).vec != 0u)
+    hipLaunchKernelGGL((update_kernel<TABS, NO, true, LAY>), dim3(grid), dim3(kUpdBlock), 0, stream,
+                       args);
   else
-    hipLaunchKernelGGL((update_kernel<TABS, NO, false>), dim3(grid), dim3(kUpdBlock), 0, stream, a);
+    hipLaunchKernelGGL((update_kernel<TABS, NO, false, LAY>), dim3(grid), dim3(kUpdBlock), 0,
+                       stream, args);
 }
 
 // LDS images: the small one keeps eight workgroups on a compute unit, the
 // large one (a group of 16 rows of a codec with k up to 255) one or two.
 constexpr int kTabsSmall = 1024, kTabsLarge = 4096;
 
-}  // namespace
-
-hipError_t launch_update(const UpdateArgs& a, uint32_t grid, hipStream_t stream) {
+// The plan kernel over the list, then the update kernel of the layout.
+template <class LAY>
+hipError_t launch_both(const typename LAY::Args& args, uint32_t grid, hipStream_t stream) {
+  const UpdateArgs& a = LAY::upd(args);
   if (a.k == 0 || a.p == 0 || a.k + a.p > 256 || a.shard_bytes == 0 || a.n_stripes == 0 ||
       a.n_updates == 0 || grid == 0)
     return hipErrorInvalidValue;
@@ -197,14 +260,29 @@ hipError_t launch_update(const UpdateArgs& a, uint32_t grid, hipStream_t stream)
   if (e != hipSuccess) return e;
   const uint32_t rows = a.p < kUpdRows ? a.p : kUpdRows;  // of the largest group
   if (rows * a.k > (uint32_t)kTabsSmall)
-    launch_one<kTabsLarge, 16>(a, grid, stream);
+    launch_one<kTabsLarge, 16, LAY>(args, grid, stream);
   else if (rows <= 4)
-    launch_one<kTabsSmall, 4>(a, grid, stream);
+    launch_one<kTabsSmall, 4, LAY>(args, grid, stream);
   else if (rows <= 8)
-    launch_one<kTabsSmall, 8>(a, grid, stream);
+    launch_one<kTabsSmall, 8, LAY>(args, grid, stream);
   else
-    launch_one<kTabsSmall, 16>(a, grid, stream);
+    launch_one<kTabsSmall, 16, LAY>(args, grid, stream);
   return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_update(const UpdateArgs& a, uint32_t grid, hipStream_t stream) {
+  return launch_both<UpdFlat>(a, grid, stream);
+}
+
+hipError_t launch_update_shards(const UpdateShardsArgs& a, uint32_t grid, hipStream_t stream) {
+  static_assert(sizeof(UpdateShardsArgs) <= 4096, "the kernel-argument block");
+  // the last block is shorter than the others, and the kernel finds it at n_full
+  if (a.tail_bytes >= a.upd.shard_bytes ||
+      a.n_full + (a.tail_bytes != 0 ? 1u : 0u) != a.upd.n_stripes)
+    return hipErrorInvalidValue;
+  return launch_both<UpdShards>(a, grid, stream);
 }
 
 }  // namespace rse

@@ -1,5 +1,5 @@
 // rse_update.hpp -- launch interface of the small-write kernels
-// (rse_update.hip) behind rse_update_flat.
+// (rse_update.hip) behind rse_update_flat and rse_update_shards.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -32,5 +32,23 @@ struct UpdateArgs {
 // workgroups (rse_update_plan.hpp update_grid), which does nothing for a
 // rejected list.
 hipError_t launch_update(const UpdateArgs& a, uint32_t grid, hipStream_t stream);
+
+// rse_update_shards' layout: one pointer per shard, and a block of
+// upd.shard_bytes of every shard in the place of a stripe -- block b of shard r
+// starts at ptr[r] + b * upd.shard_bytes, row u of new_data at
+// u * upd.shard_bytes.  upd.base is not used, and upd.n_stripes counts the
+// blocks, the shorter last one included.  The table travels in the kernel
+// arguments (2 KiB of the 4 KiB block): nothing to copy, nothing whose lifetime
+// outlasts the call.
+constexpr uint32_t kUpdMaxShards = 256;
+struct UpdateShardsArgs {
+  UpdateArgs upd;
+  uint64_t tail_bytes;  // of the last block where it is shorter than the others, else 0
+  uint32_t n_full;      // blocks of upd.shard_bytes: the index of the shorter last block
+  uint8_t* ptr[kUpdMaxShards];
+};
+
+// The same two launches; the plan kernel reads a.upd alone.
+hipError_t launch_update_shards(const UpdateShardsArgs& a, uint32_t grid, hipStream_t stream);
 
 }  // namespace rse

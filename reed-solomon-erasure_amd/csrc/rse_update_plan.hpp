@@ -5,7 +5,8 @@
 // covers, and how many workgroups are launched.  No memory access but the
 // list's own words.  Plain C++, __host__ __device__ under hipcc: the pre-pass
 // (rse_update.hip) calls the predicates the CPU test walks
-// (tests/native/update_plan.cpp).
+// (tests/native/update_plan.cpp).  At the end: what rse_update_shards adds
+// (tests/native/update_shards_plan.cpp).
 #pragma once
 
 #include <stddef.h>
@@ -93,6 +94,35 @@ inline uint32_t update_grid(uint32_t cus, int64_t grid_opt, uint64_t n_updates,
   // n_updates, spans >= 1; the product saturates
   const uint64_t items = n_updates > UINT64_MAX / spans ? UINT64_MAX : n_updates * spans;
   return (uint32_t)(items < fill ? items : fill);
+}
+
+// ---- rse_update_shards: a block of every separately allocated shard in the
+// place of a stripe (the cut itself is rse_scrub_shards_plan.hpp's).
+
+// The 16-byte path: every one of the n shard pointers and `new_data` start on
+// a 16-byte boundary, and a block's bytes and a shard's bytes are multiples of
+// 16 -- so every block starts on a boundary and the shorter last block ends on
+// one.
+inline bool update_shards_vec(const void* const* ptrs, size_t n, const void* new_data,
+                              uint64_t block_bytes, uint64_t len_bytes) {
+  bool al = reinterpret_cast<uintptr_t>(new_data) % 16u == 0 && block_bytes % 16u == 0 &&
+            len_bytes % 16u == 0;
+  for (size_t i = 0; i < n; ++i) al = al && reinterpret_cast<uintptr_t>(ptrs[i]) % 16u == 0;
+  return al;
+}
+
+// Bytes of every shard a run in `block` covers: tail_bytes in the shorter last
+// block (block n_full, where tail_bytes != 0), block_bytes in every other.
+RSE_UPD_HD uint64_t update_run_bytes(uint64_t block_bytes, uint64_t tail_bytes, uint32_t n_full,
+                                     uint32_t block) {
+  return tail_bytes != 0 && block == n_full ? tail_bytes : block_bytes;
+}
+
+// Items are counted in spans of a full block; span s of a run of run_bytes
+// has update_span_len's bytes, or none where the run ends before it (the
+// shorter last block): that item is sat out.
+RSE_UPD_HD uint64_t update_run_span_len(uint64_t run_bytes, uint64_t s) {
+  return update_span_first(s) >= run_bytes ? 0 : update_span_len(run_bytes, s);
 }
 
 }  // namespace rse

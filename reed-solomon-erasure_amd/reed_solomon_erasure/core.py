@@ -497,6 +497,46 @@ class ReedSolomon:
         return (status[:n_blocks], changed[:n_blocks], counts[:n_blocks],
                 bad_blocks[:n_blocks], n_bad)
 
+    def update(self, shards: ShardList, block_len: Optional[int], updates,
+               new_data: torch.Tensor) -> torch.Tensor:
+        """update_flat() for separately allocated shards (rse_update_shards):
+        ``shards`` and ``block_len`` as scrub() takes them, and a block of
+        ``B = min(block_len, len)`` elements of every shard (None or 0: the
+        whole shard; the last block may be shorter) in the place of a stripe.
+        ``updates`` as in update_flat() with ``{block, data shard}`` rows;
+        ``new_data`` a uint8 device tensor of exactly ``n x B`` elements, row u
+        the new contents of entry u -- an entry for a shorter last block uses
+        the start of its row.  It must not overlap the shards.  Returns the
+        ``(2,)`` int32 device tensor ``result``: ``{UPDATE_APPLIED, blocks
+        touched}``, or ``{UPDATE_REJECTED, index of the first entry out of
+        order}`` with nothing written.  Each touched block keeps its syndrome,
+        so scrub() with the same ``block_len`` repairs afterwards what it
+        would have repaired before.  Queued on the current stream, no
+        synchronisation.  Same codecs as update_flat()."""
+        if len(shards) == 0:
+            raise RSError(Error.TooFewShards)
+        ptrs, lens = _arrays(shards, self.field)
+        first = _first(shards)
+        if any(s.device != first.device for s in shards):
+            raise ValueError("shards must be on one device")
+        length = lens[0]
+        block = min(block_len or length, length)
+        upd = _update_list(updates, first.device, "shards'")
+        n = upd.shape[0]
+        if new_data.dtype != torch.uint8 or not new_data.is_contiguous():
+            raise ValueError("new_data must be a contiguous uint8 tensor")
+        if new_data.device != first.device:
+            raise ValueError("new_data must be on the shards' device")
+        need = n * block * (self.field // 8)
+        if new_data.numel() != need:
+            raise ValueError(f"new_data holds {new_data.numel()} bytes, {need} needed")
+        result = torch.zeros((2,), dtype=torch.int32, device=first.device)
+        _raise(_lib.rse_update_shards(self._h, ptrs, lens, len(shards), block_len or 0,
+                                      upd.data_ptr() if n else result.data_ptr(),
+                                      _dev(new_data) if need else result.data_ptr(), n,
+                                      result.data_ptr(), _stream(first)))
+        return result
+
     def update_flat(self, stripes: torch.Tensor, shard_len: int, n_stripes: int, updates,
                     new_data: torch.Tensor) -> torch.Tensor:
         """Rewrite data shards of the flat layout in place and patch the parity
@@ -516,23 +556,7 @@ class ReedSolomon:
         T = self.total_shard_count()
         _check_flat(stripes, shard_len, n_stripes, T, self.field)
         base = _dev(stripes)
-        if isinstance(updates, torch.Tensor) and updates.is_cuda:
-            upd = updates  # read in place, on that device
-        else:
-            rows = np.asarray(updates.cpu() if isinstance(updates, torch.Tensor) else updates)
-            if rows.size and (rows.min() < 0 or rows.max() > 0xFFFFFFFF):
-                raise ValueError("updates must hold unsigned 32-bit values")
-            if rows.size == 0:
-                rows = rows.reshape(0, 2)
-            if rows.ndim != 2 or rows.shape[1] != 2:
-                raise ValueError("updates must have shape (n, 2)")
-            rows = np.ascontiguousarray(rows.astype(np.uint32)).view(np.int32)
-            upd = torch.from_numpy(rows).to(stripes.device)
-        if (upd.dim() != 2 or upd.shape[1] != 2 or not upd.is_contiguous()
-                or upd.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32))
-                or upd.device != stripes.device):
-            raise ValueError("updates must be a contiguous (n, 2) int32/uint32 array on the "
-                             "stripes' device")
+        upd = _update_list(updates, stripes.device, "stripes'")
         n = upd.shape[0]
         if new_data.dtype != torch.uint8 or not new_data.is_contiguous():
             raise ValueError("new_data must be a contiguous uint8 tensor")
@@ -767,6 +791,29 @@ def _host_arrays(shards, field):
     pa = (ctypes.c_void_p * max(1, n))(*[_host_ptr(s) for s in shards])
     la = (ctypes.c_size_t * max(1, n))(*[_host_elems(s, field) for s in shards])
     return pa, la
+
+
+def _update_list(updates, device, whose: str) -> torch.Tensor:
+    """The update list of update_flat() / update() as an (n, 2) int32 tensor on
+    ``device``: a device tensor is taken as it is, a host array is uploaded."""
+    if isinstance(updates, torch.Tensor) and updates.is_cuda:
+        upd = updates  # read in place, on that device
+    else:
+        rows = np.asarray(updates.cpu() if isinstance(updates, torch.Tensor) else updates)
+        if rows.size and (rows.min() < 0 or rows.max() > 0xFFFFFFFF):
+            raise ValueError("updates must hold unsigned 32-bit values")
+        if rows.size == 0:
+            rows = rows.reshape(0, 2)
+        if rows.ndim != 2 or rows.shape[1] != 2:
+            raise ValueError("updates must have shape (n, 2)")
+        rows = np.ascontiguousarray(rows.astype(np.uint32)).view(np.int32)
+        upd = torch.from_numpy(rows).to(device)
+    if (upd.dim() != 2 or upd.shape[1] != 2 or not upd.is_contiguous()
+            or upd.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32))
+            or upd.device != device):
+        raise ValueError("updates must be a contiguous (n, 2) int32/uint32 array on the "
+                         f"{whose} device")
+    return upd
 
 
 def _check_host_flat(stripes, shard_len: int, n_stripes: int, total: int, field: int) -> None:
