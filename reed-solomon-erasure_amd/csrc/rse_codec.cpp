@@ -34,6 +34,8 @@
 #include "rse_scrub_shards_plan.hpp"
 #include "rse_update.hpp"
 #include "rse_update_plan.hpp"
+#include "rse_read.hpp"
+#include "rse_read_plan.hpp"
 #include "rse_correct_plan.hpp"
 #include "rse_locate.hpp"
 #include "rse_locate_plan.hpp"
@@ -2774,6 +2776,50 @@ int rse_update_shards(const rse_codec* c, void* const* shards, const size_t* len
   if (e != hipSuccess) return dev_fail(e);
   if (f != hipSuccess) return dev_fail(f);
   rse::note_kernel("update-shards gf%d %zu+%zu %s", c->field, c->k, c->p, a.vec ? "vec" : "bytes");
+  return RSE_OK;
+}
+
+// Shards read into the caller's rows, the erased ones rebuilt on the way
+// (rse_read.hip): the list pass, the run planner, the read kernel; a rejected
+// list stops the last two.  The workspace -- the verdict, the run heads, every
+// entry's class, a valid set per run and a table per (entry, input) -- is the
+// call's own.
+int rse_read_flat(const rse_codec* c, const void* stripes, size_t shard_len, size_t n_stripes,
+                  const uint8_t* present, const uint32_t* reads, size_t n_reads, void* out,
+                  uint8_t* status, uint32_t* result, rse_stream_t stream) {
+  if (!c || !stripes || !reads || !out || !status || !result) return RSE_ERR_INVALID_ARGUMENT;
+  if (!rse::read_in_scope(c->field, c->k, c->p)) return RSE_ERR_INVALID_ARGUMENT;
+  if (shard_len == 0) return RSE_EMPTY_SHARD;
+  if (n_reads == 0) return RSE_OK;
+  if (n_stripes == 0 || n_stripes > 0xffffffffu || n_reads > 0xffffffffu)
+    return RSE_ERR_INVALID_ARGUMENT;
+  RSE_ON_STREAM(stream);
+  hipStream_t st = (hipStream_t)stream;
+  int dev = 0, cus = 0;
+  RSE_HIP(hipGetDevice(&dev));
+  RSE_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+  rse::ReadArgs a{};
+  RSE_HIP(update_consts(c, dev, &a.coef));
+  a.base = static_cast<const uint8_t*>(stripes);
+  a.shard_bytes = shard_len * c->esize();
+  a.n_stripes = (uint32_t)n_stripes;
+  a.k = (uint32_t)c->k;
+  a.p = (uint32_t)c->p;
+  a.n_reads = (uint32_t)n_reads;
+  a.present = present;
+  a.reads = reads;
+  a.out = static_cast<uint8_t*>(out);
+  a.status = status;
+  a.result = result;
+  a.vec = rse::read_vec(stripes, out, a.shard_bytes) ? 1u : 0u;
+  const uint32_t grid = rse::read_grid((uint32_t)cus, rse::get_option(RSE_OPT_GRID_X), n_reads,
+                                       a.shard_bytes);
+  RSE_HIP(hipMallocAsync(reinterpret_cast<void**>(&a.ws), rse::read_ws(n_reads, a.k).bytes, st));
+  const hipError_t e = rse::launch_read(a, grid, st);
+  const hipError_t f = hipFreeAsync(a.ws, st);
+  if (e != hipSuccess) return dev_fail(e);
+  if (f != hipSuccess) return dev_fail(f);
+  rse::note_kernel("read gf%d %zu+%zu %s", c->field, c->k, c->p, a.vec ? "vec" : "bytes");
   return RSE_OK;
 }
 

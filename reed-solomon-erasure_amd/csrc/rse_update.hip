@@ -3,11 +3,12 @@
 // (encode_single's accumulation, core.rs:545-562, applied to a difference).
 //
 // Two launches on the caller's stream.  update_plan_kernel, one workgroup,
-// walks the list once: the in-order predicate of every entry
-// (rse_update_plan.hpp) with the lowest offender kept, the run heads compacted
-// in ascending order into the workspace, the verdict into the workspace and
-// into the caller's `result`.  update_kernel exits at once on a rejected list
-// -- no address is ever formed from an entry that is not in order -- and else
+// walks the list once (list_pass, rse_list_pass.hpp): the in-order predicate of
+// every entry (rse_update_plan.hpp) with the lowest offender kept, the run heads
+// compacted in ascending order into the workspace, the verdict into the
+// workspace and into the caller's `result`.  update_kernel exits at once on a
+// rejected list -- no address is ever formed from an entry that is not in order
+// -- and else
 // steps in grid strides over (run, span) items: one stripe's entries, 4 KiB of
 // every shard they name, 16 bytes per lane.  The list is strictly ascending,
 // so a run is its stripe's only writer: no atomics on shard bytes.
@@ -32,79 +33,20 @@
 // arguments, a block of columns in the place of a stripe, a shorter last block.
 #include "rse_update.hpp"
 
-#include "rse_device.hpp"
+#include "rse_list_pass.hpp"
 #include "rse_update_plan.hpp"
 
 namespace rse {
 namespace {
 
-constexpr int kPlanBlock = 1024, kPlanWaves = kPlanBlock / 64;
-constexpr uint32_t kNoOffender = 0xFFFFFFFFu;  // n_updates <= 2^32 - 1: no entry has this index
-
 __global__ __launch_bounds__(kPlanBlock) void update_plan_kernel(UpdateArgs a) {
-  __shared__ uint32_t s_wave[2][kPlanWaves];
-  __shared__ uint32_t s_bad;
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  if (threadIdx.x == 0) s_bad = kNoOffender;
-  uint32_t bad = kNoOffender, base = 0u;
-  // a head's place in the list: the heads of the trips before (base), of the
-  // waves before (through LDS, two buffers so that a trip needs one barrier)
-  // and of the lanes below
-  for (uint64_t u0 = 0, trip = 0; u0 < a.n_updates; u0 += kPlanBlock, ++trip) {
-    const uint64_t u = u0 + threadIdx.x;
-    bool head = false;
-    if (u < a.n_updates) {
-      if (bad == kNoOffender && !update_in_order(a.updates, u, a.n_stripes, a.k)) bad = (uint32_t)u;
-      head = update_run_head(a.updates, u);
-    }
-    const unsigned long long heads = __ballot(head);
-    if (lane == 0) s_wave[trip & 1u][wave] = (uint32_t)__popcll(heads);
-    __syncthreads();
-    uint32_t at = base;
-#pragma unroll
-    for (int w = 0; w < kPlanWaves; ++w) {
-      const uint32_t v = s_wave[trip & 1u][w];
-      base += v;
-      if ((uint32_t)w < wave) at += v;
-    }
-    if (head)
-      a.ws[kUpdWsList + at + (uint32_t)__popcll(heads & ((1ull << lane) - 1ull))] = (uint32_t)u;
-  }
-  if (bad != kNoOffender) atomicMin(&s_bad, bad);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const uint32_t first = s_bad;
+  uint32_t first, runs;
+  if (list_pass(a.updates, a.n_updates, a.n_stripes, a.k, a.ws + kUpdWsList, first, runs)) {
     const bool rejected = first != kNoOffender;
     a.ws[kUpdWsStatus] = rejected ? RSE_UPDATE_REJECTED : RSE_UPDATE_APPLIED;
-    a.ws[kUpdWsRuns] = base;
+    a.ws[kUpdWsRuns] = runs;
     a.result[0] = rejected ? RSE_UPDATE_REJECTED : RSE_UPDATE_APPLIED;
-    a.result[1] = rejected ? first : base;  // accepted: a run per touched stripe
-  }
-}
-
-// A lane's n <= 16 bytes at p: one 16-byte access on the vector path (n is 16
-// there), byte by byte otherwise, the bytes past n read as zero and not stored.
-template <bool VEC>
-__device__ __forceinline__ uint4 ld_lane(const uint8_t* p, uint32_t n) {
-  if constexpr (VEC) {
-    return ld16(p);
-  } else {
-    uint32_t w[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-    for (uint32_t b = 0; b < kUpdLaneBytes; ++b)
-      if (b < n) w[b / 4] |= (uint32_t)((gptr<const uint8_t>)p)[b] << (8u * (b % 4));
-    return make_uint4(w[0], w[1], w[2], w[3]);
-  }
-}
-template <bool VEC>
-__device__ __forceinline__ void st_lane(uint8_t* p, uint4 v, uint32_t n) {
-  if constexpr (VEC) {
-    st16(p, v);
-  } else {
-    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (uint32_t b = 0; b < kUpdLaneBytes; ++b)
-      if (b < n) ((gptr<uint8_t>)p)[b] = (uint8_t)(w[b / 4] >> (8u * (b % 4)));
+    a.result[1] = rejected ? first : runs;  // accepted: a run per touched stripe
   }
 }
 

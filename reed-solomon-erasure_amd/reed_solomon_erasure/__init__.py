@@ -18,10 +18,12 @@ from .core import ReedSolomon, ShardByShard  # noqa: E402
 from .core import LOCATE_CLEAN, LOCATE_LOCATED, LOCATE_UNCORRECTABLE  # noqa: E402
 from .core import CORRECT_CLEAN, CORRECT_CORRECTED, CORRECT_UNCORRECTABLE  # noqa: E402
 from .core import UPDATE_APPLIED, UPDATE_REJECTED  # noqa: E402
+from .core import READ_SERVED, READ_REJECTED, READ_COPIED, READ_REBUILT, READ_LOST  # noqa: E402
 from . import galois_8, galois_16  # noqa: E402
 
 __all__ = ["ReedSolomon", "ShardByShard", "Error", "RSError", "SBSError", "SBSErrorKind",
            "DeviceError", "galois_8", "galois_16",
            "LOCATE_CLEAN", "LOCATE_LOCATED", "LOCATE_UNCORRECTABLE",
            "CORRECT_CLEAN", "CORRECT_CORRECTED", "CORRECT_UNCORRECTABLE",
-           "UPDATE_APPLIED", "UPDATE_REJECTED"]
+           "UPDATE_APPLIED", "UPDATE_REJECTED",
+           "READ_SERVED", "READ_REJECTED", "READ_COPIED", "READ_REBUILT", "READ_LOST"]

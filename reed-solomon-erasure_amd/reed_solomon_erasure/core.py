@@ -29,6 +29,12 @@ CORRECT_UNCORRECTABLE = 2
 # rse_update_flat's result[0] (RSE_UPDATE_*)
 UPDATE_APPLIED = 0
 UPDATE_REJECTED = 1
+# rse_read_flat's result[0] and per-entry status (RSE_READ_*)
+READ_SERVED = 0
+READ_REJECTED = 1
+READ_COPIED = 0
+READ_REBUILT = 1
+READ_LOST = 2
 
 ShardList = Sequence[torch.Tensor]
 
@@ -571,6 +577,53 @@ class ReedSolomon:
                                     _dev(new_data) if need else result.data_ptr(), n,
                                     result.data_ptr(), _stream(stripes)))
         return result
+
+    def read_flat(self, stripes: torch.Tensor, shard_len: int, n_stripes: int, present, reads,
+                  out: Optional[torch.Tensor] = None
+                  ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """Read shards of the flat layout into ``out``, rebuilding the erased
+        ones on the way (rse_read_flat); ``stripes`` is only read.  ``reads`` is
+        an ``(n, 2)`` int32/uint32 array of ``{stripe, shard}`` rows in strictly
+        ascending order, any of the k + p shards -- a host array is uploaded, a
+        device tensor is read in place.  ``present`` is a uint8 device tensor of
+        ``n_stripes x (k+p)`` flags (0 = erased, its buffer is never read) or
+        None: nothing erased.  ``out`` is a uint8 device tensor of at least
+        ``n x shard_len`` elements, row u for entry u, that does not overlap
+        ``stripes``; None allocates it.  Returns ``(out, status, result)``:
+        ``status`` the ``(n,)`` uint8 device tensor of READ_COPIED,
+        READ_REBUILT (from the stripe's first k present shards in index order)
+        or READ_LOST (fewer than k present: the row is not written), and
+        ``result`` the ``(2,)`` int32 device tensor ``{READ_SERVED, entries
+        lost}``, or ``{READ_REJECTED, index of the first entry out of order}``
+        with nothing written.  Queued on the current stream, no
+        synchronisation.  galois_8 codecs and galois_16 codecs with
+        k + p <= 256, both with p <= 128."""
+        T = self.total_shard_count()
+        _check_flat(stripes, shard_len, n_stripes, T, self.field)
+        base = _dev(stripes)
+        lst = _update_list(reads, stripes.device, "stripes'")
+        n = lst.shape[0]
+        if present is not None:
+            if (not isinstance(present, torch.Tensor) or present.dtype != torch.uint8
+                    or not present.is_contiguous() or present.device != stripes.device
+                    or present.numel() != n_stripes * T):
+                raise RSError(Error.InvalidShardFlags)
+        need = n * shard_len * (self.field // 8)
+        if out is None:
+            out = torch.empty((max(1, need),), dtype=torch.uint8, device=stripes.device)[:need]
+        if out.dtype != torch.uint8 or not out.is_contiguous() or out.device != stripes.device:
+            raise ValueError("out must be a contiguous uint8 tensor on the stripes' device")
+        if out.numel() < need:
+            raise ValueError(f"out holds {out.numel()} bytes, {need} needed")
+        # at least one entry: an empty tensor has no address to pass
+        status = torch.empty((max(1, n),), dtype=torch.uint8, device=stripes.device)
+        result = torch.zeros((2,), dtype=torch.int32, device=stripes.device)
+        _raise(_lib.rse_read_flat(self._h, base, shard_len, n_stripes,
+                                  present.data_ptr() if present is not None and n_stripes else None,
+                                  lst.data_ptr() if n else result.data_ptr(), n,
+                                  _dev(out) if need else result.data_ptr(), status.data_ptr(),
+                                  result.data_ptr(), _stream(stripes)))
+        return out, status[:n], result
 
     def reconstruct_data_flat(self, stripes: torch.Tensor, shard_len: int, n_stripes: int,
                               present: Sequence[bool]) -> None:
