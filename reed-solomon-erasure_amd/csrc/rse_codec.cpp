@@ -2823,6 +2823,70 @@ int rse_read_flat(const rse_codec* c, const void* stripes, size_t shard_len, siz
   return RSE_OK;
 }
 
+// rse_read_flat for separately allocated shards, a block of block_len elements
+// of every shard in the place of a stripe: rse_update_shards' cut, checks and
+// pointer table, rse_read_flat's list pass, planner and workspace.  A NULL
+// shards[i] is a shard without a buffer: it goes into the table as it is, the
+// planner erases it in every block, and the read kernel never looks it up.
+int rse_read_shards(const rse_codec* c, const void* const* shards, const size_t* lens,
+                    size_t n_shards, size_t block_len, const uint8_t* present,
+                    const uint32_t* reads, size_t n_reads, void* out, uint8_t* status,
+                    uint32_t* result, rse_stream_t stream) {
+  if (!c || !shards || !lens || !reads || !out || !status || !result)
+    return RSE_ERR_INVALID_ARGUMENT;
+  if (!rse::read_in_scope(c->field, c->k, c->p)) return RSE_ERR_INVALID_ARGUMENT;
+  int rc;
+  if ((rc = check_count(n_shards, c->total, RSE_TOO_FEW_SHARDS, RSE_TOO_MANY_SHARDS))) return rc;
+  if ((rc = check_multi(lens, n_shards))) return rc;
+  if (n_reads == 0) return RSE_OK;
+  // the cut alone: the plan's own vec and pre-filter verdicts are the scrub's
+  const rse::ScrubShardsPlan pl =
+      rse::scrub_shards_plan(lens[0], block_len, c->esize(), shards, n_shards, false);
+  if (pl.n_blocks > 0xffffffffu || n_reads > 0xffffffffu) return RSE_ERR_INVALID_ARGUMENT;
+  static_assert(sizeof(uint8_t*) == sizeof(void*), "pointer tables");
+  if (c->total > rse::kReadMaxShards) return RSE_ERR_INVALID_ARGUMENT;  // read_in_scope: never
+  RSE_ON_STREAM(stream);
+  hipStream_t st = (hipStream_t)stream;
+  int dev = 0, cus = 0, at = -1;
+  RSE_HIP(hipGetDevice(&dev));
+  // host memory is out of scope, and the kernels would fault on it
+  for (size_t i = 0; i < n_shards; ++i)
+    if (shards[i] && !device_memory(shards[i], &at)) return RSE_ERR_INVALID_ARGUMENT;
+  if ((present && !device_memory(present, &at)) || !device_memory(reads, &at) ||
+      !device_memory(out, &at) || !device_memory(status, &at) || !device_memory(result, &at))
+    return RSE_ERR_INVALID_ARGUMENT;
+  RSE_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+  rse::ReadShardsArgs sa{};
+  rse::ReadArgs& a = sa.rd;
+  RSE_HIP(update_consts(c, dev, &a.coef));
+  a.shard_bytes = pl.block_bytes;
+  a.n_stripes = (uint32_t)pl.n_blocks;
+  a.k = (uint32_t)c->k;
+  a.p = (uint32_t)c->p;
+  a.n_reads = (uint32_t)n_reads;
+  a.present = present;
+  a.reads = reads;
+  a.out = static_cast<uint8_t*>(out);
+  a.status = status;
+  a.result = result;
+  a.vec = rse::read_shards_vec(shards, n_shards, out, pl.block_bytes,
+                               (uint64_t)lens[0] * c->esize())
+              ? 1u
+              : 0u;
+  sa.tail_bytes = pl.tail_bytes;
+  sa.n_full = (uint32_t)pl.n_full;
+  for (size_t i = 0; i < n_shards; ++i) sa.ptr[i] = static_cast<const uint8_t*>(shards[i]);
+  const uint32_t grid = rse::read_grid((uint32_t)cus, rse::get_option(RSE_OPT_GRID_X), n_reads,
+                                       pl.block_bytes);
+  RSE_HIP(hipMallocAsync(reinterpret_cast<void**>(&a.ws), rse::read_ws(n_reads, a.k).bytes, st));
+  const hipError_t e = rse::launch_read_shards(sa, grid, st);
+  const hipError_t f = hipFreeAsync(a.ws, st);
+  if (e != hipSuccess) return dev_fail(e);
+  if (f != hipSuccess) return dev_fail(f);
+  rse::note_kernel("read-shards gf%d %zu+%zu %s", c->field, c->k, c->p, a.vec ? "vec" : "bytes");
+  return RSE_OK;
+}
+
 int rse_reconstruct_data_flat(const rse_codec* c, void* stripes, size_t shard_len,
                               size_t n_stripes, const uint8_t* present, rse_stream_t stream) {
   RSE_ON_STREAM(stream);

@@ -1,4 +1,5 @@
-// rse_read.hip -- rse_read_flat: shards of the flat layout read into the
+// rse_read.hip -- rse_read_flat, rse_read_shards: shards of the flat layout
+// (at the end of this comment: of separately allocated shards) read into the
 // caller's rows, the erased ones rebuilt on the way from the first k present
 // shards of their stripe (reconstruct, core.rs:733-923, for the shards asked
 // for and into a buffer of the caller's).  `stripes` is only read.
@@ -37,6 +38,15 @@
 // A GF(2^16) codec of at most 256 shards has its matrix, and so every inverse
 // and product of it, in the GF(2^8) subfield, where a constant multiplies each
 // byte of an element by itself: the same kernels over 2 x shard_len bytes.
+//
+// rse_read_shards is the same three launches.  The list pass is shared as it
+// is.  The planner (read_shards_plan_kernel) passes read_plan_run the pointer
+// table from its arguments as the "has no buffer" predicate: a NULL shard is
+// erased in every block.  The read kernel gets another address rule
+// (ReadShards below): one pointer per shard from the kernel arguments, a block
+// of columns in the place of a stripe, a shorter last block.  It takes a shard
+// index from a run's valid set or from a copied entry and from nowhere else,
+// and the planner puts a NULL shard in neither: no address is formed from one.
 #include "rse_read.hpp"
 
 #include "rse_list_pass.hpp"
@@ -121,7 +131,10 @@ struct BlockSync {
 
 constexpr int kReadPlanBlock = 256;
 
-__global__ __launch_bounds__(kReadPlanBlock) void read_plan_kernel(ReadArgs a) {
+// The planner's body: every run's plan, with the layout's "has no buffer"
+// predicate for read_plan_run.
+template <class NoBuffer>
+__device__ __forceinline__ void read_plan_runs(const ReadArgs& a, NoBuffer no_buffer) {
   __shared__ uint8_t lg[256], ex[512];
   __shared__ uint8_t s_fl[kReadMaxShards], s_where[kReadMaxShards], s_valid[kReadMaxShards];
   __shared__ uint8_t s_S[kReadMaxP], s_R[kReadMaxP];
@@ -149,11 +162,21 @@ __global__ __launch_bounds__(kReadPlanBlock) void read_plan_kernel(ReadArgs a) {
     read_plan_run(lg, ex, a.coef, a.k, a.p,
                   a.present ? a.present + (uint64_t)stripe * T : nullptr,
                   a.reads + 2 * (uint64_t)head, n, work, emit, threadIdx.x, kReadPlanBlock,
-                  BlockSync());
+                  BlockSync(), no_buffer);
     if (s_sc[3])  // a run of a stripe that is not recoverable rebuilds nothing
       for (uint32_t i = threadIdx.x; i < a.k; i += kReadPlanBlock)
         w.valid[(uint64_t)run * a.k + i] = s_valid[i];
   }
+}
+
+__global__ __launch_bounds__(kReadPlanBlock) void read_plan_kernel(ReadArgs a) {
+  read_plan_runs(a, ReadAllBuffers());
+}
+
+// rse_read_shards: "stripe" is a block, and a shard whose pointer is NULL has
+// no buffer.  The pointers are compared, never dereferenced.
+__global__ __launch_bounds__(kReadPlanBlock) void read_shards_plan_kernel(ReadShardsArgs args) {
+  read_plan_runs(args.rd, ReadNullShards{args.ptr});
 }
 
 // Where an item's bytes lie: the addressing policy of read_kernel, in the
@@ -181,10 +204,35 @@ struct ReadFlat {
   }
 };
 
+// Separately allocated shards (rse_read_shards): ptr[shard] + block x block
+// bytes, the pointers read from the kernel arguments.  The shard index is the
+// same in every lane -- a word of the valid set, or a copied entry's shard --
+// so a pointer is a scalar load.  A run in the shorter last block has the
+// tail's bytes: fewer spans, a shorter last lane.  A row of `out` keeps the
+// full block's stride.
+struct ReadShards {
+  using Args = ReadShardsArgs;
+  static __host__ __device__ __forceinline__ const ReadArgs& rd(const Args& a) { return a.rd; }
+  static __device__ __forceinline__ uint64_t span_len(const Args& a, uint32_t block,
+                                                      uint64_t span) {
+    return update_run_span_len(update_run_bytes(a.rd.shard_bytes, a.tail_bytes, a.n_full, block),
+                               span);
+  }
+  struct At {
+    const uint8_t* const* ptr;
+    uint64_t o;
+    __device__ __forceinline__ const uint8_t* shard(uint32_t i) const { return ptr[i] + o; }
+  };
+  static __device__ __forceinline__ At at(const Args& a, uint32_t block, uint64_t off) {
+    return At{a.ptr, (uint64_t)block * a.rd.shard_bytes + off};
+  }
+};
+
 constexpr int kReadKc = 4;  // shards of the valid set a lane has in flight
 
 // NO: rows a lane accumulates, at least the entries of the call's largest
-// group.  LAY: ReadFlat (per-shard pointers would be another).
+// group.  LAY: ReadFlat or ReadShards; below, "stripe" and "shard bytes" are a
+// block and a full block's bytes for the latter.
 template <int NO, bool VEC, class LAY>
 __global__ __launch_bounds__(kUpdBlock) void read_kernel(typename LAY::Args args) {
   const ReadArgs& a = LAY::rd(args);
@@ -273,9 +321,12 @@ void launch_one(const typename LAY::Args& args, uint32_t grid, hipStream_t strea
 
 constexpr uint32_t kReadPlanGrid = 1024;  // workgroups of the planner at most, in strides over the runs
 
-}  // namespace
-
-hipError_t launch_read(const ReadArgs& a, uint32_t grid, hipStream_t stream) {
+// The list pass, the layout's planner (`plan`: the kernel, which takes the
+// layout's argument block), the read kernel of the layout.
+template <class LAY, class Plan>
+hipError_t launch_passes(const typename LAY::Args& args, uint32_t grid, hipStream_t stream,
+                         Plan plan) {
+  const ReadArgs& a = LAY::rd(args);
   if (a.k == 0 || a.p == 0 || a.p > kReadMaxP || a.k + a.p > kReadMaxShards || a.shard_bytes == 0 ||
       a.n_stripes == 0 || a.n_reads == 0 || grid == 0 ||
       reinterpret_cast<uintptr_t>(a.ws) % 16u != 0)
@@ -283,18 +334,33 @@ hipError_t launch_read(const ReadArgs& a, uint32_t grid, hipStream_t stream) {
   hipLaunchKernelGGL(read_list_kernel, dim3(1), dim3(kPlanBlock), 0, stream, a);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(read_plan_kernel, dim3(a.n_reads < kReadPlanGrid ? a.n_reads : kReadPlanGrid),
-                     dim3(kReadPlanBlock), 0, stream, a);
+  hipLaunchKernelGGL(plan, dim3(a.n_reads < kReadPlanGrid ? a.n_reads : kReadPlanGrid),
+                     dim3(kReadPlanBlock), 0, stream, args);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
   const uint32_t rows = read_max_run(a.n_reads, a.k + a.p);  // of the largest group there can be
   if (rows <= 4)
-    launch_one<4, ReadFlat>(a, grid, stream);
+    launch_one<4, LAY>(args, grid, stream);
   else if (rows <= 8)
-    launch_one<8, ReadFlat>(a, grid, stream);
+    launch_one<8, LAY>(args, grid, stream);
   else
-    launch_one<16, ReadFlat>(a, grid, stream);
+    launch_one<16, LAY>(args, grid, stream);
   return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_read(const ReadArgs& a, uint32_t grid, hipStream_t stream) {
+  return launch_passes<ReadFlat>(a, grid, stream, read_plan_kernel);
+}
+
+hipError_t launch_read_shards(const ReadShardsArgs& a, uint32_t grid, hipStream_t stream) {
+  static_assert(sizeof(ReadShardsArgs) <= 4096, "the kernel-argument block");
+  // the last block is shorter than the others, and the kernel finds it at n_full
+  if (a.tail_bytes >= a.rd.shard_bytes ||
+      a.n_full + (a.tail_bytes != 0 ? 1u : 0u) != a.rd.n_stripes)
+    return hipErrorInvalidValue;
+  return launch_passes<ReadShards>(a, grid, stream, read_shards_plan_kernel);
 }
 
 }  // namespace rse

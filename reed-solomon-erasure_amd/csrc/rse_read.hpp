@@ -1,5 +1,5 @@
 // rse_read.hpp -- launch interface of the degraded-read kernels (rse_read.hip)
-// behind rse_read_flat.
+// behind rse_read_flat and rse_read_shards.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "../../include/rse_hip.h"
+#include "rse_read_plan.hpp"
 
 namespace rse {
 
@@ -54,5 +55,23 @@ struct ReadArgs {
 // The list pass, the run planner and the read kernel over `grid` workgroups
 // (rse_read_plan.hpp read_grid); the last two do nothing for a rejected list.
 hipError_t launch_read(const ReadArgs& a, uint32_t grid, hipStream_t stream);
+
+// rse_read_shards' layout: one pointer per shard, and a block of
+// rd.shard_bytes of every shard in the place of a stripe -- block b of shard r
+// starts at ptr[r] + b * rd.shard_bytes, row u of `out` at u * rd.shard_bytes.
+// rd.base is not used, and rd.n_stripes counts the blocks, the shorter last one
+// included.  ptr[r] == nullptr: shard r has no buffer; the planner asks the
+// table itself (rse_read_plan.hpp ReadNullShards), so nothing else marks it.
+// The table travels in the kernel arguments (2 KiB of the 4 KiB block): nothing
+// to copy, nothing whose lifetime outlasts the call.
+struct ReadShardsArgs {
+  ReadArgs rd;
+  uint64_t tail_bytes;  // of the last block where it is shorter than the others, else 0
+  uint32_t n_full;      // blocks of rd.shard_bytes: the index of the shorter last block
+  const uint8_t* ptr[kReadMaxShards];
+};
+
+// The same three launches; the list pass reads a.rd alone.
+hipError_t launch_read_shards(const ReadShardsArgs& a, uint32_t grid, hipStream_t stream);
 
 }  // namespace rse

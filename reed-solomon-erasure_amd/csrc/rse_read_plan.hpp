@@ -1,12 +1,12 @@
-// rse_read_plan.hpp -- the arithmetic of one rse_read_flat call: which codecs
-// it takes, when an entry of the read list is in order, how a run's entries
+// rse_read_plan.hpp -- the arithmetic of one rse_read_flat or rse_read_shards
+// call: which codecs it takes, when an entry of the read list is in order, how a run's entries
 // are cut into output groups, whether the kernel may take its 16-byte path, how
 // many workgroups are launched, and the plan of one run: from a stripe's flag
 // row and the shards wanted of it, the valid set, every entry's class and, for
 // a rebuilt entry, its k coefficients over the valid set.  Run heads, spans
 // and lanes are rse_update_plan.hpp's.  Plain C++, __host__ __device__ under
-// hipcc: the device passes (rse_read.hip) call the functions the CPU test
-// walks (tests/native/read_plan.cpp).
+// hipcc: the device passes (rse_read.hip) call the functions the CPU tests
+// walk (tests/native/read_plan.cpp, read_shards_plan.cpp).
 #pragma once
 
 #include <stddef.h>
@@ -52,6 +52,20 @@ inline bool read_vec(const void* stripes, const void* out, uint64_t shard_bytes)
   return update_vec(stripes, out, shard_bytes);
 }
 
+// rse_read_shards' 16-byte path: every shard pointer that is there and `out`
+// start on a 16-byte boundary, and a block's bytes and a shard's bytes are
+// multiples of 16 -- so every block and every row start on a boundary and the
+// shorter last block ends on one.  A NULL pointer (a shard without a buffer)
+// decides nothing: no address is formed from it.
+inline bool read_shards_vec(const void* const* ptrs, size_t n, const void* out,
+                            uint64_t block_bytes, uint64_t len_bytes) {
+  bool al = reinterpret_cast<uintptr_t>(out) % 16u == 0 && block_bytes % 16u == 0 &&
+            len_bytes % 16u == 0;
+  for (size_t i = 0; i < n; ++i)
+    al = al && (ptrs[i] == nullptr || reinterpret_cast<uintptr_t>(ptrs[i]) % 16u == 0);
+  return al;
+}
+
 // Workgroups of the read kernel, which steps over (run, group, span) items in
 // grid strides: RSE_OPT_GRID_X > 0 sets the count outright, else what the
 // device holds at once, and no more than the items there can be -- a group has
@@ -85,6 +99,18 @@ constexpr size_t kReadWorkD = (size_t)kReadMaxP * kReadMaxP;      // of D: e x k
 // What a thread team is on the host: one thread, nothing to wait for.
 struct ReadNoSync {
   RSE_UPD_HD void operator()() const {}
+};
+
+// Which shards have no buffer: erased whatever the flag row says.  Never, for
+// the flat layout; for separately allocated shards the pointer table itself is
+// asked (rse_read_shards: shards[i] == NULL), so there is nothing beside it
+// that could disagree with it.
+struct ReadAllBuffers {
+  RSE_UPD_HD bool operator()(uint32_t) const { return false; }
+};
+struct ReadNullShards {
+  const uint8_t* const* ptr;  // k + p pointers
+  RSE_UPD_HD bool operator()(uint32_t shard) const { return ptr[shard] == nullptr; }
 };
 
 // Gauss-Jordan on the e x 2e bytes of w by the team (thread tid of nt; sync()
@@ -138,12 +164,17 @@ RSE_UPD_HD bool read_gauss_jordan(uint8_t* w, uint32_t e, const uint8_t* lg, con
 //   lg, ex   the GF(2^8) log table (256) and the doubled exp table (>= 510)
 //   P        the codec's p x k parity rows as bytes
 //   flags    the stripe's k + p flags, non-zero = present; nullptr: all present
+//   no_buffer  no_buffer(shard): the shard is erased whatever its flag says
+//            (ReadAllBuffers: none is; the overload below passes that)
 //   entries  the run's n entries, {stripe, shard} words: entries[2j + 1] is wanted
 //   emit     emit.cls(j, class) once per entry, emit.coef(j, i, c) for every
 //            rebuilt entry j and every input i < k
 // Afterwards w.valid holds the valid set -- the first k present shards in
 // index order, so the k - e present data shards and then R, the first e present
 // parity rows -- where w.sc[3] says the stripe is recoverable (k shards present).
+// Only a shard whose w.fl is set gets into the valid set or is copied, and a
+// shard without a buffer never has it set: the read kernel, which takes every
+// shard index from the valid set or from a copied entry, forms no address from it.
 // A present entry is copied; an erased one of a recoverable stripe is rebuilt,
 // else lost.  Coefficients as recon_plan_kernel (rse_kernels.hip) composes them:
 // only the e x e matrix A = P[R][S] over the missing data shards S is inverted;
@@ -153,14 +184,15 @@ RSE_UPD_HD bool read_gauss_jordan(uint8_t* w, uint32_t e, const uint8_t* lg, con
 // [input i is data d] P[r][d] + sum_u P[r][S_u] D[u][i].  Each is the unique
 // linear map from the k valid shards to the shard, so the bytes are the
 // reference's reconstruct (core.rs:733-923).
-template <class Sync, class Emit>
+template <class Sync, class Emit, class NoBuffer>
 RSE_UPD_HD void read_plan_run(const uint8_t* lg, const uint8_t* ex, const uint8_t* P, uint32_t k,
                               uint32_t p, const uint8_t* flags, const uint32_t* entries,
                               uint32_t n, const ReadRunWork& w, Emit& emit, uint32_t tid,
-                              uint32_t nt, Sync sync) {
+                              uint32_t nt, Sync sync, NoBuffer no_buffer) {
   const uint32_t T = k + p;
   sync();  // the team is done with the run before
-  for (uint32_t row = tid; row < T; row += nt) w.fl[row] = (!flags || flags[row]) ? 1 : 0;
+  for (uint32_t row = tid; row < T; row += nt)
+    w.fl[row] = ((!flags || flags[row]) && !no_buffer(row)) ? 1 : 0;
   sync();
   if (tid == 0) {
     uint32_t nv = 0, ne = 0, nr = 0;
@@ -223,6 +255,15 @@ RSE_UPD_HD void read_plan_run(const uint8_t* lg, const uint8_t* ex, const uint8_
     }
     emit.coef(j, i, (uint8_t)c);
   }
+}
+
+// Every shard has a buffer: the flat layout.
+template <class Sync, class Emit>
+RSE_UPD_HD void read_plan_run(const uint8_t* lg, const uint8_t* ex, const uint8_t* P, uint32_t k,
+                              uint32_t p, const uint8_t* flags, const uint32_t* entries,
+                              uint32_t n, const ReadRunWork& w, Emit& emit, uint32_t tid,
+                              uint32_t nt, Sync sync) {
+  read_plan_run(lg, ex, P, k, p, flags, entries, n, w, emit, tid, nt, sync, ReadAllBuffers());
 }
 
 }  // namespace rse

@@ -23,7 +23,7 @@ EXPORTS = (
     "rse_verify", "rse_verify_with_buffer", "rse_reconstruct", "rse_reconstruct_data",
     "rse_encode_flat", "rse_verify_flat", "rse_reconstruct_data_flat", "rse_reconstruct_batch",
     "rse_locate_flat", "rse_correct_flat", "rse_scrub_flat", "rse_scrub_shards", "rse_update_flat",
-    "rse_update_shards", "rse_read_flat",
+    "rse_update_shards", "rse_read_flat", "rse_read_shards",
     "rse_code_shards", "rse_code_shards_host", "rse_gf8_mul_slice", "rse_gal_mul", "rse_gal_mul_xor",
     "rse_gf16_mul_slice", "rse_gf8_invert_batch", "rse_gf16_invert_batch",
     "rse_encode_host", "rse_encode_host_flat", "rse_encode_sep_host", "rse_encode_single_host",
@@ -71,6 +71,7 @@ _SIGS = {
     "rse_update_flat": (_c.c_int, [_vp, _vp, _sz, _sz, _vp, _vp, _sz, _vp, _vp]),
     "rse_update_shards": (_c.c_int, [_vp, _vp, _szp, _sz, _sz, _vp, _vp, _sz, _vp, _vp]),
     "rse_read_flat": (_c.c_int, [_vp, _vp, _sz, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "rse_read_shards": (_c.c_int, [_vp, _vp, _szp, _sz, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
     "rse_reconstruct_data_flat": (_c.c_int, [_vp, _vp, _sz, _sz, _u8p, _vp]),
     "rse_reconstruct_batch": (_c.c_int, [_vp, _vp, _sz, _sz, _u8p, _c.c_int, _vp]),
     "rse_encode_host_flat": (_c.c_int, [_vp, _vp, _sz, _sz, _vp]),

@@ -625,6 +625,68 @@ class ReedSolomon:
                                   result.data_ptr(), _stream(stripes)))
         return out, status[:n], result
 
+    def read(self, shards, block_len: Optional[int], present, reads,
+             out: Optional[torch.Tensor] = None
+             ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """read_flat() for separately allocated shards (rse_read_shards):
+        ``shards`` and ``block_len`` as scrub() and update() take them, only
+        read, and a block of ``B = min(block_len, len)`` elements of every
+        shard (None or 0: the whole shard; the last block may be shorter) in
+        the place of a stripe.  An entry of ``shards`` may be ``None``: that
+        shard has no buffer, is erased in every block whatever ``present``
+        says, and is rebuilt or lost, never copied.  ``reads`` as in
+        read_flat() with ``{block, shard}`` rows; ``present`` a uint8 device
+        tensor of ``n_blocks x (k+p)`` flags or None.  ``out`` is a uint8
+        device tensor of at least ``n x B`` elements, row u for entry u -- an
+        entry of a shorter last block writes the start of its row -- that
+        does not overlap the shards; None allocates it.  Returns ``(out,
+        status, result)`` as read_flat() does.  Rebuilding a failed device r
+        onto a spare: ``shards[r] = None``, the list ``{b, r}`` for every
+        block, ``out`` the spare.  Queued on the current stream, no
+        synchronisation.  Same codecs as read_flat()."""
+        T = self.total_shard_count()
+        if len(shards) == 0:
+            raise RSError(Error.TooFewShards)
+        there = [s for s in shards if s is not None]
+        if not there:
+            raise ValueError("at least one shard must have a buffer")
+        first = there[0]
+        if any(s.device != first.device for s in there):
+            raise ValueError("shards must be on one device")
+        there_ptrs, there_lens = _arrays(there, self.field)
+        length = there_lens[0]
+        # a shard without a buffer: a NULL pointer and the others' length
+        at = iter(range(len(there)))
+        idx = [None if s is None else next(at) for s in shards]
+        ptrs = (ctypes.c_void_p * len(shards))(*[None if i is None else there_ptrs[i] for i in idx])
+        lens = (ctypes.c_size_t * len(shards))(*[length if i is None else there_lens[i]
+                                                 for i in idx])
+        block = min(block_len or length, length)
+        n_blocks = -(-length // block) if block else 0
+        lst = _update_list(reads, first.device, "shards'")
+        n = lst.shape[0]
+        if present is not None:
+            if (not isinstance(present, torch.Tensor) or present.dtype != torch.uint8
+                    or not present.is_contiguous() or present.device != first.device
+                    or present.numel() != n_blocks * T):
+                raise RSError(Error.InvalidShardFlags)
+        need = n * block * (self.field // 8)
+        if out is None:
+            out = torch.empty((max(1, need),), dtype=torch.uint8, device=first.device)[:need]
+        if out.dtype != torch.uint8 or not out.is_contiguous() or out.device != first.device:
+            raise ValueError("out must be a contiguous uint8 tensor on the shards' device")
+        if out.numel() < need:
+            raise ValueError(f"out holds {out.numel()} bytes, {need} needed")
+        # at least one entry: an empty tensor has no address to pass
+        status = torch.empty((max(1, n),), dtype=torch.uint8, device=first.device)
+        result = torch.zeros((2,), dtype=torch.int32, device=first.device)
+        _raise(_lib.rse_read_shards(self._h, ptrs, lens, len(shards), block_len or 0,
+                                    present.data_ptr() if present is not None and n_blocks else None,
+                                    lst.data_ptr() if n else result.data_ptr(), n,
+                                    _dev(out) if need else result.data_ptr(), status.data_ptr(),
+                                    result.data_ptr(), _stream(first)))
+        return out, status[:n], result
+
     def reconstruct_data_flat(self, stripes: torch.Tensor, shard_len: int, n_stripes: int,
                               present: Sequence[bool]) -> None:
         """wasm/src/lib.rs:57-73 over many stripes sharing one erasure pattern."""
